@@ -18,6 +18,13 @@ Extra objects on the JSON line (tier brief section 4):
                   by component counts (see `sample`): `value` = oracle/torch_port.py, the reference modules' own ATen operator sequence
                   + autograd on torch-CPU (the engine the reference runs on a CPU; kind "port" -- /root/reference is not on this box),
                   `numpy_port` = the parity oracle on the host BLAS; rank 0, N=1 only.
+These extras (and `calibration`, `hbm_copy_tbps`, `clock_ghz`) are measured only with `--full`: a plain run sets up, warms up, times the
+steps and prints the line with the headline figure (`value`, `ms_per_step`, `loss`, `config`).
+
+`--dump-outputs DIR` (rank 0): after the timed steps, what the last timed step computed is written as float32 .npy files -- `loss.npy`, and
+for every trainable parameter `param.<name>.npy` (its value after the step's AdamW update) and `grad.<name>.npy` (the step's gradient),
+each a fixed seeded sample of at most 8192 elements (whole tensors below that).  Inputs and weights are seeded, so two builds compare file
+for file.
 """
 from __future__ import annotations
 
@@ -38,6 +45,33 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA peak (MI355X_MICROARCH.md; vendor 5 PF figure is 2:1 sparse)
+DUMP_SAMPLE = 8192         # elements per tensor in --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, named_params):
+    """--dump-outputs: the loss of the last timed step and, per trainable parameter, the same seeded sample of its updated value and of its
+    gradient (indices from the parameter's name, so they do not depend on the build).  Float32; at most DUMP_MAX_BYTES in all."""
+    import zlib
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    total = 4
+    for name, p in named_params:
+        n = p.numel()
+        idx = None
+        if n > DUMP_SAMPLE:
+            rng = np.random.default_rng([20261016, zlib.crc32(name.encode())])
+            idx = torch.from_numpy(np.sort(rng.integers(0, n, DUMP_SAMPLE))).to(p.device)
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            a = (flat if idx is None else flat.index_select(0, idx)).float().cpu().numpy()
+            total += a.nbytes
+            if total > DUMP_MAX_BYTES:
+                raise SystemExit("bench.py: --dump-outputs would exceed %d bytes" % DUMP_MAX_BYTES)
+            np.save(os.path.join(path, "%s.%s.npy" % (kind, name)), a)
 
 
 
@@ -296,19 +330,24 @@ def run_c5(args, device, rank, world, use_dist):
     from otter_amd import ops as _ops
 
     rM, rN, rK = text["intermediate_size"], text["hidden_size"], B * S
-    _ops.prof_arm_gemm(rM, rN, rK, max_events=max(64, args.steps * text["num_hidden_layers"] + 8))
+    if args.full:
+        _ops.prof_arm_gemm(rM, rN, rK, max_events=max(64, args.steps * text["num_hidden_layers"] + 8))
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     sync()
     elapsed = time.perf_counter() - t0
-    n_launch, gemm_ms, _, _ = _ops.prof_collect_split()
-    _ops.prof_disarm()
+    n_launch = 0
+    if args.full:
+        n_launch, gemm_ms, _, _ = _ops.prof_collect_split()
+        _ops.prof_disarm()
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, [(n, p) for n, p in model.named_parameters() if p.requires_grad])
     if rank == 0:
         roof = None
         if n_launch > 0:
@@ -322,9 +361,9 @@ def run_c5(args, device, rank, world, use_dist):
         # memory statistics FIRST: the calibration probes below allocate 2 GiB of copy buffers of their own
         mem = {"peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1), "reserved_mem_gb": round(torch.cuda.max_memory_reserved() / 2**30, 1),
                "alloc_retries": int(torch.cuda.memory_stats().get("num_alloc_retries", 0))}
-        cal = machine_calibration(device) if world == 1 else None
+        cal = machine_calibration(device) if world == 1 and args.full else None
         cpu_b, cpu_note = None, None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:      # a reported extra must never cost the bench line
                 cpu_b = cpu_baseline_c5(B, S, text)
             except Exception as ex:
@@ -339,9 +378,9 @@ def run_c5(args, device, rank, world, use_dist):
                        "every parameter trainable (%.2f B), bf16 autocast, fp32 masters" % (B, S, text_len, n_par / 1e9),
                        "global_batch": B * world, "seq_len": S, "parallelism": "dp%d" % world},
             "loss": round(float(loss), 4),
-            "roofline": roof,
-            "cpu_baseline": cpu_b,
             "model_tflops_per_s": round(flops * args.steps / elapsed / 1e12, 1), **mem}
+        if args.full:
+            line["roofline"], line["cpu_baseline"] = roof, cpu_b
         if cpu_note:
             line["cpu_baseline_note"] = cpu_note
         apply_calibration(line, roof, cal)
@@ -706,6 +745,11 @@ def main():
     ap.add_argument("--config", choices=["c2", "c4", "c5"], default="c2",
                     help="c2 = OTTER-Image-MPT7B (BASELINE metric, the default); c4 = OTTER-Video-LLaMA7B, 8 frames per sample (configs[3]); "
                          "c5 = OtterHD / Fuyu-8B full fine-tune, 1080x1080 patch tokens (configs[4]; batch 8 as in the reference's OtterHD recipe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extras of the line: roofline (GEMM launches timed in the steps, the stand-alone gated block), "
+                         "calibration (MFMA / copy probes, the in-step GEMM clock) and cpu_baseline; off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (loss, sampled updated parameters and gradients) as float32 .npy files to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--gemm-variant", type=int, default=0)
     ap.add_argument("--flash-variant", type=int, default=0, help="A/B hook: otter_flash_set_variant (2 = plain grid order instead of longest-first)")
@@ -824,7 +868,8 @@ def main():
         torch.cuda.current_stream().synchronize()
         _K.check(_K.lib().otter_debug_occupy_cus(n_occ, occ_flag.data_ptr(), 60 * 100_000_000, side.cuda_stream), "occupy_cus")
     M, N, Kd = B * T, 16384, 4096
-    ops.prof_arm_gemm(M, N, Kd, max_events=max(64, args.steps * 8 * 3 + 8))
+    if args.full:
+        ops.prof_arm_gemm(M, N, Kd, max_events=max(64, args.steps * 8 * 3 + 8))
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -834,12 +879,16 @@ def main():
     if n_occ:
         occ_flag.fill_(1)
         torch.cuda.synchronize()
-    n_launch, gemm_ms, n_km, km_ms = ops.prof_collect_split()
-    ops.prof_disarm()
+    n_launch = 0
+    if args.full:
+        n_launch, gemm_ms, n_km, km_ms = ops.prof_collect_split()
+        ops.prof_disarm()
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, [(n, p) for n, p in model.named_parameters() if p.requires_grad])
 
     if rank == 0:
         pairs = B * world * args.steps
@@ -903,9 +952,10 @@ def main():
                        # the rest from the sweep; "sweep" = every gradient (OTTER_NO_FUSED_GRAD_NORM=1, or a DP reducer is attached)
                        "grad_norm": ("fused:%d" % step.optimizer.fused_norm_tensors) if getattr(step, "norm_sink", None) is not None else "sweep"},
             "loss": round(float(loss), 4),
-            "roofline": roof,
         }
-        if world == 1 and not n_occ:
+        if args.full:
+            out["roofline"] = roof
+        if world == 1 and not n_occ and args.full:
             cal = machine_calibration(device)
             try:
                 cal["in_step_gemm"] = in_step_gemm_clock(one_step)      # (one more optimizer step, after everything that is reported)
@@ -913,7 +963,7 @@ def main():
                 cal["in_step_gemm"] = None
                 cal["calibration_note"] = (cal.get("calibration_note", "") + " in-step clock failed: %r" % (ex,)).strip()
             apply_calibration(out, roof, cal)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:      # a reported extra must never cost the bench line (host OOM, a transformers API change ...)
                 out["cpu_baseline"] = cpu_baseline(T, args.config)
             except Exception as ex:

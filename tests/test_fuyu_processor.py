@@ -1,18 +1,19 @@
 """otter_amd.processing_fuyu.FuyuProcessor: the reference's OtterHD collate (pipeline/mimicit_utils/mimicit_dataset.py:497-505)
 calls `fuyu_processor(text=, images=)`, `.get_labels(...)` and `.find_and_remove_tokens(...)`; the library class the shim used to re-export
-has neither method and pads on the other side.  Where /root/reference exists (the build container) the reference's own methods are the
-expected values; everywhere the hand-worked cases below run."""
-import importlib.util
+has neither method and pads on the other side.  Expected values: the hand-worked cases below, and what the reference's own methods
+returned on the seeded batches, recorded in tests/golden/fuyu_processor_ref.npz (oracle/gen_golden_processor.py)."""
 import os
 import types
 
+import numpy as np
 import pytest
 import torch
 
 from otter_amd.processing_fuyu import FuyuProcessor
 
-REF = "/root/reference/src/otter_ai/models/fuyu/processing_fuyu.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fuyu_processor_ref.npz")
 EOS, SPECIAL = 7, 71122
+SEEDS = (0, 1, 2)
 
 
 def _proc():
@@ -22,23 +23,9 @@ def _proc():
     return p
 
 
-def _ref_proc():
-    if not os.path.exists(REF):
-        return None
-    import sys
-    name = "transformers.models.fuyu.image_processing_fuyu"    # needs torchvision (absent here); the reference only takes FuyuBatchFeature from it
-    if name not in sys.modules:
-        try:
-            importlib.import_module(name)
-        except ImportError:
-            sys.modules[name] = types.SimpleNamespace(FuyuBatchFeature=dict)
-    spec = importlib.util.spec_from_file_location("_ref_processing_fuyu", REF)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    r = mod.FuyuProcessor.__new__(mod.FuyuProcessor)
-    r.tokenizer = types.SimpleNamespace(eos_token_id=EOS)
-    r.pad_token_id, r.dummy_image_index = EOS, -1
-    return r
+def _recorded():
+    with np.load(GOLDEN) as z:
+        return {k: torch.from_numpy(z[k]) for k in z.files}
 
 
 def _batch(seed, B=6, T=24, n_special=(0, 2, 2, 3, 4, 2)):
@@ -66,19 +53,17 @@ def test_find_and_remove_tokens_hand_case():
     assert ids.tolist() == new_ids.tolist()          # the reference writes through row views: the caller's tensors change too
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="needs /root/reference (build container)")
-@pytest.mark.parametrize("seed", [0, 1, 2])
+@pytest.mark.parametrize("seed", SEEDS)
 def test_labels_and_token_rewrite_equal_the_reference(seed):
-    ref, mine = _ref_proc(), _proc()
-    ids = _batch(seed)
-    want = ref.get_labels(ids.clone(), SPECIAL)
+    rec, mine = _recorded(), _proc()
+    r = {k: rec["s%d_%s" % (seed, k)] for k in ("ids", "labels", "new_ids", "new_labels", "ids_after", "labels_after")}
+    ids, want = r["ids"], r["labels"]
     got = mine.get_labels(ids.clone(), SPECIAL)
     assert torch.equal(got, want)
-    a_ids, a_lab = ids.clone(), want.clone()
     b_ids, b_lab = ids.clone(), want.clone()
-    w = ref.find_and_remove_tokens(a_ids, a_lab, SPECIAL)
     g = mine.find_and_remove_tokens(b_ids, b_lab, SPECIAL)
-    assert torch.equal(g[0], w[0]) and torch.equal(g[1], w[1]) and torch.equal(a_ids, b_ids) and torch.equal(a_lab, b_lab)
+    assert torch.equal(g[0], r["new_ids"]) and torch.equal(g[1], r["new_labels"])
+    assert torch.equal(b_ids, r["ids_after"]) and torch.equal(b_lab, r["labels_after"])
 
 
 def _encodings():
@@ -94,11 +79,9 @@ def test_right_padding_with_attention_mask():
     assert [tuple(p.shape) for p in out["image_patches"]] == [(1, 4, 6), (1, 6, 6)]
     left = _proc()._left_pad_inputs_with_attention_mask(_encodings(), True)
     assert left["input_ids"][0].tolist() == [EOS, EOS, EOS, 100, 101, 102, 103, 104] and left["attention_mask"][0].tolist() == [0] * 3 + [1] * 5
-    ref = _ref_proc()
-    if ref is not None:
-        w = ref._right_pad_inputs_with_attention_mask(_encodings(), True)
-        for k in ("input_ids", "attention_mask", "image_patches_indices"):
-            assert torch.equal(out[k], w[k]), k
+    rec = _recorded()
+    for k in ("input_ids", "attention_mask", "image_patches_indices"):
+        assert torch.equal(torch.as_tensor(out[k]), rec["right_pad_" + k]), k
 
 
 def test_call_encodes_each_pair_alone_then_right_pads(monkeypatch):

@@ -3,7 +3,7 @@
 # Legs: baseline | 16 CUs pinned by otter_debug_occupy_cus | + one-workgroup-per-tile grids for the own GEMMs | + hipBLASLt stream-K grids
 # capped at 240 CUs | the cap alone.   usage: tools/occupy_ab.sh [n_cus] [out]
 N=${1:-16}; OUT=${2:-gpurun_out/occupy_ab.txt}; CAP=$((256 - N))
-run() { echo -n "$1 : " >> $OUT; env $2 timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>&1 | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'],'pairs/s',d['ms_per_step'],'ms/step, FFN GEMM',d['roofline']['avg_us'],'us')" >> $OUT; }
+run() { echo -n "$1 : " >> $OUT; env $2 timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>&1 | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'],'pairs/s',d['ms_per_step'],'ms/step, FFN GEMM',d['roofline']['avg_us'],'us')" >> $OUT; }
 : > $OUT
 run "baseline                                            " "A=1"
 run "$N CUs occupied                                     " "OTTER_BENCH_OCCUPY_CUS=$N"

@@ -6,7 +6,7 @@ OUT=gpurun_out/r06d_env_ab.txt
 : > $OUT
 run() { # label, env...
   local label=$1; shift
-  env "$@" timeout 600 python bench.py --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" timeout 600 python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ OUT=gpurun_out/r06d_m0group_step_ab.txt
 for r in 1 2 3 4; do
   for leg in grouped per_piece; do
     if [ $leg = per_piece ]; then export OTTER_LIB_PATH=$OLD; else unset OTTER_LIB_PATH; fi
-    timeout 600 python bench.py --steps 16 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ OUT=gpurun_out/r06d_modes_ab.txt
 : > $OUT
 for r in 1 2 3; do
   for mode in mlp 1t attn 1; do
-    OTTER_OWN_DECODER_GEMM=$mode timeout 600 python bench.py --steps 16 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
+    OTTER_OWN_DECODER_GEMM=$mode timeout 600 python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

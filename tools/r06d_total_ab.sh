@@ -16,7 +16,7 @@ done
 for r in 1 2 3 4; do
   for v in r6d r6c; do
     if [ $v = r6c ]; then export OTTER_LIB_PATH=$OLD; else unset OTTER_LIB_PATH; fi
-    timeout 600 python bench.py --steps 16 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

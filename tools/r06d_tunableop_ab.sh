@@ -17,7 +17,7 @@ ls -la gpurun_out/r06d_tunableop_results*.csv >> $OUT 2>&1
 for r in 1 2 3; do
   for leg in default tuned; do
     if [ $leg = tuned ]; then export PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=0 PYTORCH_TUNABLEOP_FILENAME=$CSV; else unset PYTORCH_TUNABLEOP_ENABLED PYTORCH_TUNABLEOP_TUNING PYTORCH_TUNABLEOP_FILENAME; fi
-    timeout 600 python bench.py --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

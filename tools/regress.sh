@@ -7,7 +7,7 @@
 TAG=${1:-r05}; ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$ROOT/gpurun_out; mkdir -p $OUT
 cd $ROOT
 echo "== bench (default line, calibration inside) =="
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_regress_bench.json 2> $OUT/${TAG}_regress_bench.err; cut -c1-1500 $OUT/${TAG}_regress_bench.json
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_regress_bench.json 2> $OUT/${TAG}_regress_bench.err; cut -c1-1500 $OUT/${TAG}_regress_bench.json
 echo "== per-shape GEMMs: own vs hipBLASLt, warm / cold operands (tools/gemm_cold_ab.py) =="
 timeout 200 python tools/gemm_cold_ab.py > $OUT/${TAG}_regress_gemm_cold_ab.txt 2>&1; cat $OUT/${TAG}_regress_gemm_cold_ab.txt
 echo "== every GEMM launch of the gated block, one by one (tools/block_gemm_times.py) =="
