@@ -340,6 +340,32 @@ int otter_decode_attn(const void* q, int64_t q_batch_stride, int64_t q_head_stri
                       int64_t head_dim, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_persimmon_decode_attn -- one cached decode step of the OtterHD / Fuyu-8B (Persimmon) attention
+ * (fuyu/modeling_persimmon.py:262-312 with a past_key_value and one new token): q / k LayerNorm over the 64-wide head and the
+ * partial rotary embedding on their first `rot` dims at position S_past (the arithmetic of otter_qk_norm_rope_fwd), the new key and
+ * value appended to the cache, and the single query's softmax(q k^T * scale) v over all S_past + 1 keys -- one pass.
+ *   qkv      [B, H, 3, 64] bf16 contiguous: q | k | v of the new token per head (the projection output, read in place)
+ *   gamma_q / beta_q / gamma_k / beta_k  fp32 [64]; cos_row / sin_row fp32 [rot]: the rotary table row of position S_past
+ *   k_past / v_past  bf16, indexed [b, h, key, dim] (key < S_past) through explicit batch / head / key strides in elements, dim
+ *            stride 1 and every stride a multiple of 8 (contiguous caches, the strided views the flash prefill returns and
+ *            index_select results all qualify).  Read only: never written.
+ *   key_valid  uint8 [B, S_past + 1] (0 = padded key) or NULL.  A row with every key masked gives o = 0.
+ *   k_new / v_new  bf16 [B, H, S_past + 1, 64] contiguous, caller-allocated, not overlapping the past: rows 0..S_past-1 = the past
+ *            (bit copies), row S_past = the normalised + rotated k (bf16) and the raw v.
+ *   o        [B, H * 64] bf16 contiguous (the input of `dense`).
+ *   workspace  fp32 scratch of at least OTTER_PERSIMMON_DECODE_WORKSPACE_BYTES(B, H, S_past + 1) bytes (split partials).
+ * head_dim 64 only; rot a multiple of 16 in (0, 64]; S_past >= 1 and S_past + 1 <= 65536 keys.  The keys of each (batch, head)
+ * are split across workgroups when B * H is small next to the CU count; the ranges are combined in a fixed order (deterministic).
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_PERSIMMON_DECODE_WORKSPACE_BYTES(B, H, Sk) ((int64_t)(B) * (int64_t)(H) * (((int64_t)(Sk) + 127) / 128) * 66 * 4)
+int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
+                                const float* cos_row, const float* sin_row, const void* k_past, int64_t k_batch_stride, int64_t k_head_stride,
+                                int64_t k_key_stride, int64_t k_dim_stride, const void* v_past, int64_t v_batch_stride, int64_t v_head_stride,
+                                int64_t v_key_stride, int64_t v_dim_stride, const uint8_t* key_valid, void* k_new, void* v_new, void* o,
+                                void* workspace, int64_t workspace_bytes, int64_t B, int64_t H, int64_t S_past, int64_t head_dim, int64_t rot,
+                                float eps, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * OtterHD / Fuyu-8B path (config C5): row-wise kernels of the Persimmon decoder and the patch scatter.
  *   otter_qk_norm_rope_fwd  /root/reference/src/otter_ai/models/fuyu/modeling_persimmon.py:262-304: the per-head interleaved
  *       projection output qkv [tokens, H, 3, 64] (bf16) is read in place; q and k get LayerNorm over the 64-wide head

@@ -1131,14 +1131,15 @@ class PersimmonAttentionFn(torch.autograd.Function):
     (Round 2 zero-padded q / k / v / dO to 128 columns and gathered ctx from a padded output: `_persimmon_pad128`.)"""
 
     @staticmethod
-    def forward(ctx, qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, scale):
+    def forward(ctx, qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, scale, key_valid=None):
         B, S, _ = qkv.shape
         qkv = qkv.contiguous()
         gqf, bqf, gkf, bkf = (t.detach().float().contiguous() for t in (gq, bq, gk, bk))
         pad = _persimmon_pad128(H)
         q, k, v, stats = ops.qk_norm_rope_fwd(qkv, gqf, bqf, gkf, bkf, cos, sin, H, rot, eps, width=128 if pad else 64, copy_v=pad)
-        o, lse = ops.flash_attn_fwd(q, k, v, None, None, scale, True)            # [B,S,H,128 | 64]
+        o, lse = ops.flash_attn_fwd(q, k, v, None, key_valid, scale, True)       # [B,S,H,128 | 64]
         ctx.save_for_backward(qkv, stats, q, k, v, o, lse, gqf, gkf, cos, sin)
+        ctx.key_valid = key_valid
         ctx.cfg = (H, rot, scale, gq.dtype, pad)
         k_c, v_c = k[..., :64], v[..., :64]          # normalised + rotated keys and the values, for a KV cache (not differentiable)
         ctx.mark_non_differentiable(k_c, v_c)
@@ -1153,7 +1154,7 @@ class PersimmonAttentionFn(torch.autograd.Function):
             do = torch.zeros((B, S, H, 128), dtype=torch.bfloat16, device=qkv.device)
             do[..., :64] = dctx.reshape(B, S, H, 64)
             dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-            ops.flash_attn_bwd(q, k, v, o, lse, do, dq, dk, dv, None, None, scale, True)
+            ops.flash_attn_bwd(q, k, v, o, lse, do, dq, dk, dv, None, ctx.key_valid, scale, True)
             dqkv, dgq, dbq, dgk, dbk = ops.qk_norm_rope_bwd(dq, dk, dv, qkv, stats, gqf, gkf, cos, sin, H, rot)
         else:
             do = dctx.reshape(B, S, H, 64)
@@ -1161,15 +1162,16 @@ class PersimmonAttentionFn(torch.autograd.Function):
             dqkv = torch.empty_like(qkv)
             dq, dk = torch.empty_like(q), torch.empty_like(k)
             dv = dqkv.view(B, S, H, 3, 64)[:, :, :, 2]
-            ops.flash_attn_bwd(q, k, v, o, lse, do, dq, dk, dv, None, None, scale, True)
+            ops.flash_attn_bwd(q, k, v, o, lse, do, dq, dk, dv, None, ctx.key_valid, scale, True)
             dqkv, dgq, dbq, dgk, dbk = ops.qk_norm_rope_bwd(dq, dk, None, qkv, stats, gqf, gkf, cos, sin, H, rot, dqkv=dqkv)
-        return dqkv, dgq.to(pdt), dbq.to(pdt), dgk.to(pdt), dbk.to(pdt), None, None, None, None, None, None
+        return dqkv, dgq.to(pdt), dbq.to(pdt), dgk.to(pdt), dbk.to(pdt), None, None, None, None, None, None, None
 
 
-def persimmon_attention(qkv, q_ln, k_ln, cos, sin, n_heads, rot, scale, want_kv=False):
-    """ctx [B,S,H*64], or (ctx, k [B,H,S,64], v [B,H,S,64]) with want_kv (the layout of the plain path's cache)."""
+def persimmon_attention(qkv, q_ln, k_ln, cos, sin, n_heads, rot, scale, want_kv=False, key_valid=None):
+    """ctx [B,S,H*64], or (ctx, k [B,H,S,64], v [B,H,S,64]) with want_kv (the layout of the plain path's cache).  key_valid: uint8 [B,S]
+    key-padding mask (a left-padded prompt) or None."""
     ctx, k_c, v_c = PersimmonAttentionFn.apply(qkv, q_ln.weight, q_ln.bias, k_ln.weight, k_ln.bias, cos.contiguous(), sin.contiguous(), n_heads,
-                                               rot, q_ln.eps, scale)
+                                               rot, q_ln.eps, scale, key_valid)
     if want_kv:
         return ctx, k_c.transpose(1, 2), v_c.transpose(1, 2)
     return ctx

@@ -21,6 +21,9 @@ bf16 GPU path (every parameter is trainable here, so the GEMMs are torch / hipBL
                                          and padded q / k / v / dO / o copies; still used for an odd head count, OTTER_FUYU_PAD128=1.)
   squared-ReLU                           csrc/fuyu.hip: otter_sqrelu_fwd / _bwd
   patch embeddings into the sequence     csrc/fuyu.hip: otter_scatter_rows (+ gather for the backward)
+  cached decode step (S = 1, no grad)    csrc/persimmon_decode.hip: otter_persimmon_decode_attn -- q/k LayerNorm + rotary of the new token,
+                                         the cache append (one read of the past, one write of the new cache) and the single-query
+                                         attention in one pass; OTTER_FUYU_HIP_DECODE=0 keeps the plain path (A/B switch)
 fp32 / CPU: the plain PyTorch expression of the same arithmetic (parity mode; pinned by tests/golden/fuyu_tiny.npz, generated
 by the reference's own FuyuForCausalLM)."""
 from __future__ import annotations
@@ -36,6 +39,7 @@ from transformers import FuyuConfig, PersimmonConfig, PreTrainedModel
 from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
 
 from . import functional as OF
+from . import ops
 
 
 def _rotate_half(x):
@@ -91,15 +95,37 @@ class PersimmonAttention(nn.Module):
         return (x.is_cuda and OF.compute_dtype_for(x) == torch.bfloat16 and self.head_dim == 64 and self.qk_layernorm and self.rot % 16 == 0
                 and 0 < self.rot <= 64 and s_past == 0 and default_pos and os.environ.get("OTTER_NO_FLASH") != "1")
 
-    def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False):
+    def _ln_f32(self):
+        """fp32 contiguous (gamma_q, beta_q, gamma_k, beta_k) for the decode kernel, refreshed when a parameter changes."""
+        ps = (self.q_layernorm.weight, self.q_layernorm.bias, self.k_layernorm.weight, self.k_layernorm.bias)
+        key = tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
+        c = getattr(self, "_ln32", None)
+        if c is None or c[0] != key:
+            c = (key, tuple(p.detach().float().contiguous() for p in ps))
+            self._ln32 = c
+        return c[1]
+
+    def decode_step(self, x, cos_row, sin_row, past_key_value, key_valid, use_cache):
+        """Cached decode step on HIP (x [B,1,D] bf16, no autograd): the projection, then q/k LayerNorm + rotary at position S_past, the
+        cache append and the single-query attention in one kernel (csrc/persimmon_decode.hip), then `dense`.  The past is read, never
+        written: the new cache is a fresh [B,H,S_past+1,64] pair, as the plain path's torch.cat makes it."""
+        B = x.shape[0]
+        qkv = OF.trainable_linear(self.query_key_value, x)                      # [B,1,H*3*64]
+        gq, bq, gk, bk = self._ln_f32()
+        o, k, v = ops.persimmon_decode_attn(qkv.view(B, self.n_heads, 3, 64), gq, bq, gk, bk, cos_row, sin_row, past_key_value[0],
+                                            past_key_value[1], key_valid, self.rot, self.q_layernorm.eps, self.scale)
+        return OF.trainable_linear(self.dense, o.view(B, 1, self.hidden)), ((k, v) if use_cache else None)
+
+    def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False, key_valid=None):
         B, S, _ = x.shape
         H, d = self.n_heads, self.head_dim
         qkv = OF.trainable_linear(self.query_key_value, x)                      # [B,S,H*3*d], per head (q | k | v)
         if hip:
+            kw = {} if key_valid is None else {"key_valid": key_valid}
             if use_cache:
-                ctx, k, v = OF.persimmon_attention(qkv, self.q_layernorm, self.k_layernorm, cos, sin, H, self.rot, self.scale, want_kv=True)
+                ctx, k, v = OF.persimmon_attention(qkv, self.q_layernorm, self.k_layernorm, cos, sin, H, self.rot, self.scale, want_kv=True, **kw)
                 return OF.trainable_linear(self.dense, ctx), (k, v)
-            ctx = OF.persimmon_attention(qkv, self.q_layernorm, self.k_layernorm, cos, sin, H, self.rot, self.scale)
+            ctx = OF.persimmon_attention(qkv, self.q_layernorm, self.k_layernorm, cos, sin, H, self.rot, self.scale, **kw)
             return OF.trainable_linear(self.dense, ctx), None
         q5 = qkv.view(B, S, H, 3, d)
         q, k, v = q5[..., 0, :], q5[..., 1, :], q5[..., 2, :]
@@ -132,16 +158,22 @@ class PersimmonDecoderLayer(nn.Module):
         self.input_layernorm = nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)
         self.post_attention_layernorm = nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)
 
-    def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False, pending=None, defer=False):
+    def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False, pending=None, defer=False, key_valid=None,
+                decode=None):
         """hip path: `pending` is the previous layer's MLP output, not yet added to the residual stream -- the add rides in this layer's
-        first LayerNorm pass; with `defer` the layer hands its own MLP output back the same way ((x, past, mlp_out) instead of (x, past))."""
+        first LayerNorm pass; with `defer` the layer hands its own MLP output back the same way ((x, past, mlp_out) instead of (x, past)).
+        `key_valid`: uint8 [B,S] key-padding mask of a left-padded prompt (inference only); `decode` = (cos_row, sin_row): the cached
+        one-token step on csrc/persimmon_decode.hip against `past_key_value` (key_valid then [B,S_past+1])."""
         if hip:
             n1, n2 = self.input_layernorm, self.post_attention_layernorm
             if pending is not None:
                 x, a = OF.add_layer_norm(x, pending, n1.weight, n1.bias, n1.eps, torch.bfloat16)   # x = x + pending ; a = LN(x)  (one pass)
             else:
                 a = OF.layer_norm(x, n1.weight, n1.bias, n1.eps, torch.bfloat16)
-            b, new_past = self.self_attn(a, cos, sin, use_cache=use_cache, hip=True)
+            if decode is not None:
+                b, new_past = self.self_attn.decode_step(a, decode[0], decode[1], past_key_value, key_valid, use_cache)
+            else:
+                b, new_past = self.self_attn(a, cos, sin, use_cache=use_cache, hip=True, key_valid=key_valid)
             x, m = OF.add_layer_norm(x, b, n2.weight, n2.bias, n2.eps, torch.bfloat16)   # x = x + b ; m = LN(x)  (one pass)
             if defer:
                 return x, new_past, self.mlp(m)
@@ -197,6 +229,25 @@ class PersimmonModel(PersimmonPreTrainedModel):
             self._tab = (emb.cos().contiguous(), emb.sin().contiguous())
         return self._tab
 
+    def _hip_decode_ok(self, x, past_key_values, s_past, default_pos) -> bool:
+        """The cached one-token step on csrc/persimmon_decode.hip: CUDA, bf16 compute, S == 1 after a prompt, default positions, q/k
+        LayerNorm, rot % 16 == 0, no autograd, and every layer's past a bf16 [B,H,S_past,64] pair the kernel reads in place."""
+        B, S = x.shape[:2]
+        att = self.layers[0].self_attn
+        if not (x.is_cuda and S == 1 and s_past > 0 and default_pos and OF.compute_dtype_for(x) == torch.bfloat16 and att.head_dim == 64
+                and att.qk_layernorm and att.rot % 16 == 0 and 0 < att.rot <= 64 and s_past + 1 <= ops.PERSIMMON_DECODE_MAX_KEYS
+                and os.environ.get("OTTER_FUYU_HIP_DECODE", "1") != "0" and os.environ.get("OTTER_NO_FLASH") != "1"):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        if len(past_key_values) < len(self.layers):
+            return False
+        for i in range(len(self.layers)):
+            pkv = past_key_values[i]
+            if pkv is None or len(pkv) != 2 or not all(t.is_cuda and ops._decode_past_ok(t, B, att.n_heads, s_past) for t in pkv):
+                return False
+        return True
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, use_cache=None,
                 return_dict=True, **unused):
         if (input_ids is None) == (inputs_embeds is None):
@@ -223,10 +274,23 @@ class PersimmonModel(PersimmonPreTrainedModel):
             if bool(am.all()):
                 am = None
         # HIP path: causal only, like the reference's flash_attn_func(causal=True) which never sees the padding mask
-        # (modeling_persimmon.py:310): with right padding the real positions are identical; left padding takes the plain path
-        hip = self.layers[0].self_attn.hip_ok(x, s_past, default_pos) and (am is None or bool(am[:, 0].all()))
+        # (modeling_persimmon.py:310): with right padding the real positions are identical.  A left-padded prompt without autograd
+        # (generate()) runs it too, with the key-padding mask evaluated in the flash kernel (pad-query rows, whose keys are all masked,
+        # come out as 0: finite); under autograd left padding takes the plain path
+        key_valid = None
+        hip = self.layers[0].self_attn.hip_ok(x, s_past, default_pos)
+        if hip and am is not None and not bool(am[:, 0].all()):
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+                hip = False
+            else:
+                key_valid = am[:, -s_k:].to(torch.uint8).contiguous()
+        # cached one-token step on csrc/persimmon_decode.hip (the plain path's mask semantics on key_valid)
+        dec = None
+        if not hip and self._hip_decode_ok(x, past_key_values, s_past, default_pos):
+            dec = (cos_t[s_past], sin_t[s_past])
+            key_valid = am[:, -s_k:].to(torch.uint8).contiguous() if am is not None else None
         mask = None
-        if not hip:
+        if not hip and dec is None:
             neg = torch.finfo(torch.float32).min
             mask = torch.zeros(1, 1, S, s_k, dtype=torch.float32, device=x.device)
             if S > 1:
@@ -239,8 +303,9 @@ class PersimmonModel(PersimmonPreTrainedModel):
         pending = None      # hip path: a layer's MLP output joins the residual stream inside the NEXT LayerNorm pass (one kernel less per layer)
         for i, layer in enumerate(self.layers):
             pkv = past_key_values[i] if (past_key_values is not None and len(past_key_values) > i) else None
-            if hip:
-                x, npkv, pending = layer(x, cos, sin, use_cache=use_cache, hip=True, pending=pending, defer=True)
+            if hip or dec is not None:
+                x, npkv, pending = layer(x, cos, sin, past_key_value=pkv, use_cache=use_cache, hip=True, pending=pending, defer=True,
+                                         key_valid=key_valid, decode=dec)
             else:
                 x, npkv = layer(x, cos, sin, attn_mask=mask, past_key_value=pkv, use_cache=use_cache)
             if use_cache:
@@ -426,6 +491,10 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
                 w = self.vision_embed_tokens
                 if torch.is_tensor(image_patches):
                     pe = list(w(image_patches.to(w.weight.dtype)))                  # one GEMM for the whole batch
+                elif (len(image_patches) and all(p.dim() == 3 and p.shape[0] == 1 and p.shape == image_patches[0].shape for p in image_patches)):
+                    # the processor's list of same-size [1, n, patch_dim] images: the same single GEMM as the tensor form, so both forms give
+                    # the same bits (per-image GEMMs of another row count may round differently, depending on the BLAS kernel chosen)
+                    pe = list(w(torch.cat([p.to(w.weight.dtype) for p in image_patches], 0)))
                 else:
                     pe = [w(p.to(w.weight.dtype)).squeeze(0) for p in image_patches]
                 inputs_embeds = self.gather_continuous_embeddings(inputs_embeds, pe, image_patches_indices)

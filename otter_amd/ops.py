@@ -485,6 +485,58 @@ def decode_attn(q, k, v, slopes, key_valid, scale):
     return o
 
 
+PERSIMMON_DECODE_MAX_KEYS = 65536      # include/otter_hip.h: S_past + 1 <= 65536
+
+
+def persimmon_decode_workspace_bytes(B: int, H: int, Sk: int) -> int:
+    """OTTER_PERSIMMON_DECODE_WORKSPACE_BYTES of include/otter_hip.h."""
+    return B * H * ((Sk + 127) // 128) * 66 * 4
+
+
+def _decode_past_ok(t, B, H, S_past) -> bool:
+    return (t.dtype == torch.bfloat16 and t.dim() == 4 and tuple(t.shape) == (B, H, S_past, 64) and t.stride(3) == 1
+            and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(2) % 8 == 0 and t.data_ptr() % 16 == 0)
+
+
+def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past, key_valid, rot, eps, scale):
+    """One cached Persimmon decode step (otter_persimmon_decode_attn).  qkv [B,H,3,64] bf16 contiguous (the new token's projection, per
+    head q|k|v); gq / bq / gk / bk fp32 [64]; cos_row / sin_row fp32 [rot] (position S_past); k_past / v_past bf16 [B,H,S_past,64] with a
+    unit dim stride and strides that are multiples of 8 (read only); key_valid uint8 [B,S_past+1] or None.
+    Returns (o [B,H*64], k_new [B,H,S_past+1,64], v_new [B,H,S_past+1,64]), all bf16 and freshly allocated."""
+    K.require_cuda(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past, key_valid)
+    if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[2:] != (3, 64) or not qkv.is_contiguous():
+        raise K.OtterHipError("persimmon_decode_attn: qkv must be contiguous bf16 [B,H,3,64]")
+    B, H = qkv.shape[:2]
+    S_past = k_past.shape[2] if k_past.dim() == 4 else -1
+    if S_past < 1 or S_past + 1 > PERSIMMON_DECODE_MAX_KEYS:
+        raise K.OtterHipError(f"persimmon_decode_attn: past length {S_past} outside [1, {PERSIMMON_DECODE_MAX_KEYS - 1}]")
+    if not _decode_past_ok(k_past, B, H, S_past) or not _decode_past_ok(v_past, B, H, S_past):
+        raise K.OtterHipError("persimmon_decode_attn: k_past / v_past must be bf16 [B,H,S_past,64], unit dim stride, strides % 8 == 0, 16-B aligned")
+    for t in (gq, bq, gk, bk):
+        if t.dtype != torch.float32 or t.numel() != 64 or not t.is_contiguous():
+            raise K.OtterHipError("persimmon_decode_attn: gamma / beta must be contiguous fp32 [64]")
+    if rot <= 0 or rot > 64 or rot % 16:
+        raise K.OtterHipError(f"persimmon_decode_attn: rot={rot} must be a multiple of 16 in (0, 64]")
+    for t in (cos_row, sin_row):
+        if t.dtype != torch.float32 or t.numel() != rot or not t.is_contiguous():
+            raise K.OtterHipError("persimmon_decode_attn: cos_row / sin_row must be contiguous fp32 [rot]")
+    Sk = S_past + 1
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or not key_valid.is_contiguous() or tuple(key_valid.shape) != (B, Sk)):
+        raise K.OtterHipError("persimmon_decode_attn: key_valid must be contiguous uint8 [B,S_past+1]")
+    k_new = torch.empty((B, H, Sk, 64), dtype=torch.bfloat16, device=qkv.device)
+    v_new = torch.empty_like(k_new)
+    o = torch.empty((B, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    nbytes = persimmon_decode_workspace_bytes(B, H, Sk)
+    ws = _ws.get(nbytes, qkv.device)
+    K.check(K.lib().otter_persimmon_decode_attn(qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_row.data_ptr(),
+                                                sin_row.data_ptr(), k_past.data_ptr(), k_past.stride(0), k_past.stride(1), k_past.stride(2),
+                                                k_past.stride(3), v_past.data_ptr(), v_past.stride(0), v_past.stride(1), v_past.stride(2),
+                                                v_past.stride(3), K.ptr(key_valid), k_new.data_ptr(), v_new.data_ptr(), o.data_ptr(), ws.data_ptr(),
+                                                ws.numel(), B, H, S_past, 64, int(rot), float(eps), float(scale), K.stream()),
+            "persimmon_decode_attn")
+    return o, k_new, v_new
+
+
 def qk_norm_rope_fwd(qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, width=128, copy_v=True):
     """qkv [B,S,H*3*64] bf16 (per head q|k|v) -> q', k', v as [B,S,H,width] bf16, stats [B*S,H,2,2].  width 128: upper 64 columns zero
     (the 128-wide flash kernels); width 64: compact heads (the head-pair kernels), and with copy_v=False v is returned as the strided
