@@ -173,9 +173,9 @@ int otter_gemm_kmajor_supported(int64_t M, int64_t N, int64_t K, int64_t lda, in
 /* selects the bf16 kernel schedule: 0 = auto, 1 = 128x128 register-staged, 2 = 256x256 register-staged,
  * 3 = 256x256 direct-to-LDS (global_load_lds).  Process-wide; for A/B measurements. */
 int otter_gemm_set_variant(int variant);
-/* 1 if `variant` is compiled into this library.  The product build carries 0-3, 13, 25, 26 (the kernels pick_cfg can choose);
- * the earlier kernel generations (4-12, 14-23, 27-29) live in the tools-only experimental build
- * (`python -m otter_amd.build --experimental` -> lib/libotter_hip_experimental.so, -DOTTER_EXPERIMENTAL). */
+/* 1 if `variant` is compiled into this library: 0-3, 13, 25, 26, 30 (the kernels pick_cfg can choose).  The numbers of the earlier
+ * kernel generations (4-12, 14-23, 27-29) are retired: otter_gemm_set_variant refuses them with OTTER_ERR_UNSUPPORTED
+ * (DESIGN_HISTORY.md names the last commit that holds their source). */
 int otter_gemm_variant_available(int variant);
 /* Caps the persistent GEMM grids at `cus` workgroups (0 = every CU of the device, the default; values below 8 are raised to 8).
  * Returns the grid size now in effect.  Used by the data-parallel step: with `cus` a little below the device's CU count, RCCL's

@@ -15,14 +15,23 @@
 //   * XCD-aware block order: consecutive (swizzled) ids sweep M inside one N panel, and each XCD gets a contiguous
 //     chunk of that order, so a weight panel is fetched into one XCD's L2 once.
 // f32 kernel (parity mode, exact f32): v_mfma_f32_32x32x2_f32, 64x64x32 tile, padded LDS rows.
+//
+// Variant numbers (otter_gemm_set_variant; 0 = auto = pick_cfg) -> kernel -> when pick_cfg chooses it:
+//   1   gemm_bf16_kernel<128,128,2,2,false>  fewer than 192 tiles of 256x256 and the ring does not apply; fallback of 25 / 30
+//   2   gemm_bf16_kernel<256,256,2,4,false>  never by itself: fallback of 3 / 13 / 26 for K % 64 != 0
+//   3   gemm_bf16_kernel<256,256,2,4,true>   never by itself: fallback of 13 / 26 for an operand of >= 4 GB (K % 64 == 0)
+//   13  gemm_bf16_ph_kernel                  >= 192 tiles of 256x256 and K % 128 != 0 (K % 64 == 0)
+//   25  gemm_bf16_s4_kernel                  fewer than 192 such tiles, K % 256 == 0, K >= 512, at most 512 tiles of 128x128
+//   30  gemm_bf16_s4h_kernel                 as 25 with at most 160 tiles of 128x128 and no gate partials (gemm_impl; OTTER_NO_S4H=1: off)
+//   26  gemm_bf16_t4_kernel<EPI,TA,TB,XT>    >= 192 tiles of 256x256 and K % 128 == 0: the default of the FFN shapes.  XT (cross-tile ring) for
+//                                            K-contiguous operands with K >= 256; TA / TB for K-major operands (otter_gemm)
+//   fp32 operands: gemm_f32_kernel, always.  Numbers 4-12, 14-23 and 27-29 are retired (DESIGN_HISTORY.md).
 #include "common.h"
 #include <type_traits>
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-thread_local char g_otter_err[512] = {0};
 
 // Diagnostics (otter_gemm_set_debug bit 64 + otter_gemm_read_timeline): tile-phase timestamps (s_memtime, shader cycles) of
 // the one-wave-per-SIMD kernels, blocks 0 and 131, every wave, the first 8 tiles of the block:
@@ -31,22 +40,17 @@ thread_local char g_otter_err[512] = {0};
 // and the launch's shape + operand layout (mark 7: M in 20 bits, N, K in 21 bits each, bits 63 / 62 = A / B K-major).
 __device__ unsigned long long g_gemm_timeline[2 * 4 * 8 * 8];
 
-// tools-only ablation builds of variant 26's K loop (-DOTTER_T4_ABL=mask; build.build_gemm_define): 1 = no LDS-DMA inside the K loop, 2 = no fragment
-// reads, 4 = no workgroup barriers, 8 = no waits for the LDS-DMA, 16 = a piece's scalar instructions without its buffer_load.  Timing only -- the results are wrong by construction; the product build has mask 0.
+// Measuring instruments, compile-time, tools only (`python -m otter_amd.build --define OTTER_T4_ABL=<mask> <suffix>`): ablation builds of variant 26's
+// K loop -- 1 = no LDS-DMA inside the K loop, 2 = no fragment reads, 4 = no workgroup barriers, 8 = no waits for the LDS-DMA, 16 = a piece's scalar
+// instructions without its buffer_load.  Timing only -- the results are wrong by construction; the product build has mask 0.
 #ifndef OTTER_T4_ABL
 #define OTTER_T4_ABL 0
 #endif
-// cross-tile K-contiguous instantiations of variant 26: M0 written once per four LDS-DMA pieces (1 default; 0 = one s_mov per piece: the A/B build)
-#ifndef OTTER_T4_M0GROUP
-#define OTTER_T4_M0GROUP 1
-#endif
-// ... and the scalar source offsets of a K-tile computed on three free slots of the schedule (0 default; 1 = in one burst in front of the K-tile: the A/B build)
-// ... and that M0 written one MFMA slot before the group's first piece (1 default; 0 = in the piece's own slot, with an s_nop: the A/B build)
-#ifndef OTTER_T4_M0EARLY
-#define OTTER_T4_M0EARLY 1
-#endif
-#ifndef OTTER_T4_SETK_BURST
-#define OTTER_T4_SETK_BURST 0
+// ... and of the fused tails (-DOTTER_DIAG=mask; `python -m otter_amd.build --diag N`): 4 = the tail without its global loads / stores, 128 = plain
+// (cacheable, write-back) stores instead of non-temporal ones.  Compile-time on purpose: a run-time flag inside the K-loop lambdas cost the product
+// kernels 3-4x.
+#ifndef OTTER_DIAG
+#define OTTER_DIAG 0
 #endif
 namespace {
 
@@ -84,10 +88,6 @@ __device__ __forceinline__ void load4(const void* p, int64_t idx, int dt, float 
 // Outputs are written once and not re-read by this kernel: non-temporal stores keep them from displacing the operand
 // panels in the XCD's L2 (and from being written back in the middle of the next tile's K loop).
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-#ifndef OTTER_DIAG
-#define OTTER_DIAG 0
-#endif
 // diag bit 128: plain (cacheable, write-back) stores in the fused tail instead of non-temporal ones (timing experiment)
 template <typename V>
 __device__ __forceinline__ void out_store(V v, V* p) {
@@ -331,15 +331,6 @@ __device__ __forceinline__ float epilogue8(const GemmArgs& g, float s, int64_t m
 // demoted the accumulators to scratch; an out-of-line body took its arguments through flat (generic) pointers.
 constexpr int EPI_LD = 68;  // floats per parked row (64 + 4 pad; rows stay 16-B aligned)
 
-// Compile-time diagnostics for the ablation builds of tools/gemm_ablate.py (`python -m otter_amd.build --diag N` writes
-// lib/libotter_hip_diagN.so; results are WRONG by construction).  Phased kernel only: 1 = no DMA, 2 = no MFMA,
-// 4 = epilogue without its global loads/stores, 8 = no ds_read of fragments, 16 = no epilogue at all (accumulators are
-// only summed so that the MFMAs stay live), 32 = half the A-fragment reads, 64 = half the DMA pieces.  Compile-time on purpose: a runtime flag inside the K-loop lambdas cost the
-// product kernels 3-4x.
-#ifndef OTTER_DIAG
-#define OTTER_DIAG 0
-#endif
-
 template <int EPI>
 __device__ __forceinline__ float epilogue_stripe(const GemmArgs& g, float s, const float* __restrict__ blk, int64_t m_base,
                                                  int64_t n_base, int lane) {
@@ -404,7 +395,7 @@ __device__ __forceinline__ void block_partial(const GemmArgs& g, float part, flo
     }
 }
 
-// ---- fast tail of the one-wave-per-SIMD kernels (variants 17-20), FULL tiles only ----
+// ---- fast tail of the one-wave-per-SIMD kernels (variants 25, 26, 30; written for the retired 17-20), FULL tiles only ----
 // With 8 waves per CU the stripe loop above hides its own latencies (another wave always has something to issue); with one
 // wave per SIMD every ds_write -> ds_read -> global access chain is exposed, and the run-time switches of the generic tail
 // (output dtype, bounds, wide/narrow) sit inside its loops: the K sweep of tools/gemm_ksweep.py priced the fixed part of a
@@ -989,32 +980,27 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_kernel(GemmArgs g) {
     }  // persistent tile loop
 }
 
-#ifdef OTTER_EXPERIMENTAL  // tools-only: variant 8: wave-specialised kernel (8 MFMA waves + 4 loader waves)
-#include "experimental/gemm_ws_variant8.inc"
-#endif
-
 // ------------------------------------------------------------------------------------------------------------
-// bf16 phased kernel (variant 6): the 256x256x64 / 8-wave / LDS-DMA kernel above with the K-tile split into four
-// quadrant phases and the two wave rows STAGGERED by one barrier (guide section 5, "8-phase" idea):
+// bf16 phased kernel (variant 13, the fallback for K % 128 != 0): the 256x256x64 / 8-wave / LDS-DMA tile of gemm_bf16_kernel
+// with the K-tile split into four quadrant phases and the two wave rows STAGGERED by one barrier:
 //   wave (wr, wc) owns rows wr*128.. x cols wc*64..; phase (mh, nh) = its 64x32 quadrant x the whole BK = 8 MFMAs.
-//   per phase:  LOAD part (ds_read the quadrant's new fragments [+ issue the next tile's DMA in phase 0])
+//   per phase:  LOAD part (ds_read the quadrant's new fragments + two DMA pieces of the next K-tile)
 //               | s_barrier | lgkmcnt(0) | setprio(1) 8x MFMA setprio(0) | s_barrier
 //   waves 4-7 (wr = 1) execute one extra s_barrier up front, so at every moment one wave row sits in its MFMA cluster
 //   while the other sits in its LOAD part.  A SIMD hosts wave s (wr 0) and wave s+4 (wr 1): its matrix pipe is fed by
 //   the two alternately and LDS reads / DMA issue of one always run under the MFMAs of the other.
 // Hazards (barrier instance k of row 0 pairs with instance k+1 of row 1):
-//   RAW  DMA(t+1) -> ds_read: every wave waits vmcnt(0) in the LOAD part of phase 3, i.e. before a barrier that both its
-//        own row and (one instance later) the other row pass before their first read of tile t+1.
-//   WAR  ds_read(t-1) -> DMA(t+1) into the same buffer: phase 3 reads nothing new (the nh=0 B fragments are kept in
-//        registers) and phase 2's reads are retired by lgkmcnt(0) before its MFMAs, so when any wave issues the DMA in
-//        phase 0 of tile t every read of tile t-1 has completed, on both rows.
+//   RAW  DMA(t+1) -> ds_read: counted vmcnt in the LOAD part of the phase before the one that reads the half-tile, i.e.
+//        before a barrier that both its own row and (one instance later) the other row pass before their first read.
+//   WAR  ds_read(t-1) -> DMA(t+1) into the same buffer: phase 3 reads nothing new (both nh fragments of B stay in
+//        registers) and every phase's reads are retired by lgkmcnt(0) before its MFMAs, so a half-tile is refilled only
+//        after its last read has completed, on both rows.
+// (The six other schedules this kernel once carried, with and without buffer addressing -- variants 6, 7, 9-11, 14-16 -- are retired: DESIGN_HISTORY.md.)
 // ------------------------------------------------------------------------------------------------------------
-template <int EPI, int SCH, bool BUF>
+template <int EPI>
 __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(GemmArgs g) {
-    constexpr bool CNT = SCH >= 1;
     constexpr int BM = 256, BN = 256, NT = 512;
     constexpr int TILE_BYTES = (BM + BN) * 128;
-    constexpr int CH = 4;  // 16-B chunks per thread per operand per K-tile
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1023,13 +1009,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(GemmArgs g) {
     const bf16_t* __restrict__ B = (const bf16_t*)g.B;
     const int nk = (int)(g.K >> 6);
     const float sgate = g.gate ? tanhf(*g.gate) : 1.0f;
-    // BUF: buffer addressing for the DMA (SGPR resource descriptor + 32-bit per-lane offset + scalar K offset): no
-    // per-piece 64-bit VALU address arithmetic, and the hardware range check clamps reads past the end of the operand
-    __amdgpu_buffer_rsrc_t rsrc_a, rsrc_b;
-    if constexpr (BUF) {
-        rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(A), 0, (int)(uint32_t)((g.M - 1) * g.lda * 2 + g.K * 2), 0x00020000);
-        rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(B), 0, (int)(uint32_t)((g.N - 1) * g.ldb * 2 + g.K * 2), 0x00020000);
-    }
+    // buffer addressing for the DMA (SGPR resource descriptor + 32-bit per-lane offset + scalar K offset): no per-piece
+    // 64-bit VALU address arithmetic, and the hardware range check clamps reads past the end of the operand (the host
+    // guarantees the operands span < 4 GB)
+    const __amdgpu_buffer_rsrc_t rsrc_a =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(A), 0, (int)(uint32_t)((g.M - 1) * g.lda * 2 + g.K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_b =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(B), 0, (int)(uint32_t)((g.N - 1) * g.ldb * 2 + g.K * 2), 0x00020000);
     const int ntiles = g.gm * g.gn;
 #define RAW_BARRIER()                       \
     do {                                    \
@@ -1041,89 +1027,38 @@ __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(GemmArgs g) {
         int tile_m, tile_n;
         tile_of_block(g, vb, tile_m, tile_n);
         const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-        // global side: 32-bit per-lane byte offsets from a wave-uniform base (SGPR base + VGPR offset addressing: half the
-        // address registers of 64-bit pointers and no per-tile 64-bit VALU adds; the host guarantees the operands span < 4 GB)
-        uint32_t oa[CH], ob[CH];
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int c = i * NT + tid, row = c >> 3, phys = c & 7;
-            const int slot = phys ^ ((row >> 1) & 7);
-            int64_t ga = m0 + row; if (ga > g.M - 1) ga = g.M - 1;
-            int64_t gb = n0 + row; if (gb > g.N - 1) gb = g.N - 1;
-            oa[i] = (uint32_t)((ga * g.lda + slot * 8) * 2);
-            ob[i] = (uint32_t)((gb * g.ldb + slot * 8) * 2);
-        }
-        auto stage = [&](int buf, int kt) {
-            if constexpr ((OTTER_DIAG & 1) != 0) return;
-            const char* abase = reinterpret_cast<const char*>(A) + (size_t)kt * 128;
-            const char* bbase = reinterpret_cast<const char*>(B) + (size_t)kt * 128;
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int wbase = buf * TILE_BYTES + (i * NT + wave * 64) * 16;
-                if constexpr (BUF)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(smem + wbase), 16,
-                                                             (int)oa[i], kt * 128, 0, 0);
-                else
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(abase + oa[i]),
-                                                 (__attribute__((address_space(3))) void*)(smem + wbase), 16, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                const int wbase = buf * TILE_BYTES + BM * 128 + (i * NT + wave * 64) * 16;
-                if constexpr (BUF)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(smem + wbase), 16,
-                                                             (int)ob[i], kt * 128, 0, 0);
-                else
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bbase + ob[i]),
-                                                 (__attribute__((address_space(3))) void*)(smem + wbase), 16, 0, 0);
-            }
-        };
-        // CNT schedule: the K-tile is fed as four half-tiles of 128 rows -- A_h(mh) = rows {wr*128 + mh*64 + 0..63 : wr},
+        // The K-tile is fed as four half-tiles of 128 rows -- A_h(mh) = rows {wr*128 + mh*64 + 0..63 : wr},
         // B_h(nh) = rows {wc*64 + nh*32 + 0..31 : wc} -- i.e. exactly the rows ONE quadrant phase reads.  Two DMA pieces per
         // thread per half-tile; they are issued one or two per phase and retired with COUNTED vmcnt (never drained in
         // steady state): A_h0,B_h0(t+1) in phase 0, B_h1(t+1) in phase 1, A_h1(t+1) in phase 2 -> every half-tile has three
         // phases to land and the wait in phase q-1 for the rows phase q reads leaves the 2-3 newest half-tiles in flight.
         uint32_t oah[2][2], obh[2][2];
-        if constexpr (CNT) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
+        for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int c = i * NT + tid, rl = c >> 3, phys = c & 7;
-                    const int ra = (rl >> 6) * 128 + h * 64 + (rl & 63);
-                    const int rb = (rl >> 5) * 64 + h * 32 + (rl & 31);
-                    int64_t ga = m0 + ra; if (ga > g.M - 1) ga = g.M - 1;
-                    int64_t gb = n0 + rb; if (gb > g.N - 1) gb = g.N - 1;
-                    oah[h][i] = (uint32_t)((ga * g.lda + (phys ^ ((ra >> 1) & 7)) * 8) * 2);
-                    obh[h][i] = (uint32_t)((gb * g.ldb + (phys ^ ((rb >> 1) & 7)) * 8) * 2);
-                }
-        }
-        auto stage_ah = [&](int buf, int kt, int h, int i0 = 0, int i1 = 2) {
-            if constexpr ((OTTER_DIAG & 1) != 0) return;
-            const char* abase = reinterpret_cast<const char*>(A) + (size_t)kt * 128;
+            for (int i = 0; i < 2; ++i) {
+                const int c = i * NT + tid, rl = c >> 3, phys = c & 7;
+                const int ra = (rl >> 6) * 128 + h * 64 + (rl & 63);
+                const int rb = (rl >> 5) * 64 + h * 32 + (rl & 31);
+                int64_t ga = m0 + ra; if (ga > g.M - 1) ga = g.M - 1;
+                int64_t gb = n0 + rb; if (gb > g.N - 1) gb = g.N - 1;
+                oah[h][i] = (uint32_t)((ga * g.lda + (phys ^ ((ra >> 1) & 7)) * 8) * 2);
+                obh[h][i] = (uint32_t)((gb * g.ldb + (phys ^ ((rb >> 1) & 7)) * 8) * 2);
+            }
+        auto stage_ah = [&](int buf, int kt, int h) {
 #pragma unroll
-            for (int i = i0; i < ((OTTER_DIAG & 64) ? (i1 < 1 ? i1 : 1) : i1); ++i) {  // diag 64: half the DMA pieces
+            for (int i = 0; i < 2; ++i) {
                 const int wbase = buf * TILE_BYTES + (i * 128 + h * 64 + wave * 8) * 128;
-                if constexpr (BUF)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(smem + wbase), 16,
-                                                             (int)oah[h][i], kt * 128, 0, 0);
-                else
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(abase + oah[h][i]),
-                                                 (__attribute__((address_space(3))) void*)(smem + wbase), 16, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(smem + wbase), 16,
+                                                         (int)oah[h][i], kt * 128, 0, 0);
             }
         };
-        auto stage_bh = [&](int buf, int kt, int h, int i0 = 0, int i1 = 2) {
-            if constexpr ((OTTER_DIAG & 1) != 0) return;
-            const char* bbase = reinterpret_cast<const char*>(B) + (size_t)kt * 128;
+        auto stage_bh = [&](int buf, int kt, int h) {
 #pragma unroll
-            for (int i = i0; i < ((OTTER_DIAG & 64) ? (i1 < 1 ? i1 : 1) : i1); ++i) {
+            for (int i = 0; i < 2; ++i) {
                 const int wbase = buf * TILE_BYTES + BM * 128 + ((2 * i + (wave >> 2)) * 64 + h * 32 + (wave & 3) * 8) * 128;
-                if constexpr (BUF)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(smem + wbase), 16,
-                                                             (int)obh[h][i], kt * 128, 0, 0);
-                else
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bbase + obh[h][i]),
-                                                 (__attribute__((address_space(3))) void*)(smem + wbase), 16, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(smem + wbase), 16,
+                                                         (int)obh[h][i], kt * 128, 0, 0);
             }
         };
         // LDS side: the swizzle term (row>>1)&7 only depends on lane&31 (every row offset used below is a multiple of 32),
@@ -1137,20 +1072,14 @@ __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(GemmArgs g) {
             lb[ks] = BM * 128 + (wc * 64 + (lane & 31)) * 128 + (slot << 4);
         }
         auto ld_a = [&](int buf, int mh, bf16x8_t (&fa)[2][4]) {
-            if constexpr ((OTTER_DIAG & 8) != 0) return;
             const char* base = smem + buf * TILE_BYTES + mh * (64 * 128);
 #pragma unroll
-            for (int mi2 = 0; mi2 < ((OTTER_DIAG & 32) ? 1 : 2); ++mi2)
+            for (int mi2 = 0; mi2 < 2; ++mi2)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
                     fa[mi2][ks] = *reinterpret_cast<const bf16x8_t*>(base + la[ks] + mi2 * (32 * 128));
-            if constexpr ((OTTER_DIAG & 32) != 0) {  // half the A fragment reads
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fa[1][ks] = fa[0][ks];
-            }
         };
         auto ld_b = [&](int buf, int nh, bf16x8_t (&fb)[4]) {
-            if constexpr ((OTTER_DIAG & 8) != 0) return;
             const char* base = smem + buf * TILE_BYTES + nh * (32 * 128);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) fb[ks] = *reinterpret_cast<const bf16x8_t*>(base + lb[ks]);
@@ -1168,269 +1097,45 @@ __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(GemmArgs g) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                              \
         __builtin_amdgcn_s_setprio(1);                                                                                  \
-        _Pragma("unroll") for (int ks = 0; ks < ((OTTER_DIAG & 2) ? 0 : 4); ++ks) {                                    \
+        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                              \
             acc[(MH)*2 + 0][NH] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FB[ks], FA[0][ks], acc[(MH)*2 + 0][NH], 0, 0, 0); \
             acc[(MH)*2 + 1][NH] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FB[ks], FA[1][ks], acc[(MH)*2 + 1][NH], 0, 0, 0); \
         }                                                                                                               \
         __builtin_amdgcn_s_setprio(0);                                                                                  \
     } while (0)
 
-        if constexpr (CNT) {
-            stage_ah(0, 0, 0); stage_bh(0, 0, 0); stage_bh(0, 0, 1); stage_ah(0, 0, 1);
-        } else {
-            stage(0, 0);
-        }
-        if constexpr (SCH == 2 || SCH == 4) {
-            if (nk > 1) { stage_ah(1, 1, 0); stage_bh(1, 1, 0); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if constexpr (SCH == 6) {
-            if (nk > 1) {
-                stage_ah(1, 1, 0); stage_bh(1, 1, 0); stage_bh(1, 1, 1); stage_ah(1, 1, 1);
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        stage_ah(0, 0, 0); stage_bh(0, 0, 0); stage_bh(0, 0, 1); stage_ah(0, 0, 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (wr == 1) RAW_BARRIER();  // stagger the second wave row by one barrier
-        bf16x8_t fa[2][4], fb[4];
-        [[maybe_unused]] bf16x8_t fb1[4];
-        if constexpr ((OTTER_DIAG & 8) != 0) {  // fragments without LDS reads: lane-dependent, non-zero
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                fb[ks] = __builtin_bit_cast(bf16x8_t, uint4{0x3f803f80u + (unsigned)lane, 0x3f003f00u, 0x3e803e80u, 0x3f803f80u});
-                fa[0][ks] = fa[1][ks] = fb[ks];
-                fb1[ks] = fb[ks];
-            }
-        }
-        if constexpr (SCH == 6) {
-            // Deep-queue schedule: every half-tile slot is refilled ONE phase after its only read, with the data of tile
-            // t+2 (same buffer), instead of one K-tile later with tile t+1's -- 10-12 DMA pieces per wave in flight
-            // instead of 4-6 (the L2->LDS stream is latency x concurrency bound: DESIGN.md 4.1).
-            //   reads  : phase 0: A_h0,B_h0   1: B_h1   2: A_h1   3: -          (B fragments stay in fb / fb1)
-            //   refill : phase 1: A_h0(t+2)   2: B_h0(t+2)   3: B_h1(t+2), A_h1(t+2)   (ds_read / DMA = 12/0 4/2 8/2 0/4)
-            // WAR: fragment reads are retired (lgkmcnt(0)) BEFORE the first barrier of their phase; the other row passes
-            // the matching barrier before its next LOAD part, so a refill issued one phase later can never overtake a read.
-            // RAW: counted vmcnt in the phase before the read, before that phase's first barrier (as in the other schedules).
-            for (int t = 0; t < nk; ++t) {
-                const int cur = t & 1;
-                const int e = nk - 1 - t;  // K-tiles after this one
-                // ---- phase 0: quadrant (0,0) ----
-                ld_a(cur, 0, fa);
-                ld_b(cur, 0, fb);
-                if (e >= 1) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 0, fa, fb);
-                RAW_BARRIER();
-                // ---- phase 1: quadrant (0,1) ----
-                ld_b(cur, 1, fb1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (e >= 2) { stage_ah(cur, t + 2, 0); asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); }
-                else if (e == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 1, fa, fb1);
-                RAW_BARRIER();
-                // ---- phase 2: quadrant (1,1) ----
-                ld_a(cur, 1, fa);
-                __builtin_amdgcn_sched_barrier(0);
-                if (e >= 2) stage_bh(cur, t + 2, 0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(1, 1, fa, fb1);
-                RAW_BARRIER();
-                // ---- phase 3: quadrant (1,0) ----
-                if (e >= 2) { stage_bh(cur, t + 2, 1); stage_ah(cur, t + 2, 1); asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); }
-                else if (e == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(1, 0, fa, fb);
-                RAW_BARRIER();
-            }
-        } else if constexpr (SCH == 5) {
-            // Two phases per K-tile (16 MFMAs per cluster, 4 workgroup barriers per K-tile instead of 8):
-            //   phase A: reads A0,B0,B1 (16) + 6 DMA pieces [A_h0,B_h0,B_h1](t+1) | quadrants (0,0),(0,1)
-            //   phase B: reads A1 (8)       + 2 DMA pieces  A_h1(t+1)            | quadrants (1,1),(1,0)
-            // The fragment reads are retired (lgkmcnt(0)) BEFORE the first barrier of their phase, so once a row has
-            // passed that barrier none of its reads of the buffer is pending: the other row may refill it right away.
-            for (int t = 0; t < nk; ++t) {
-                const int cur = t & 1;
-                const bool more = t + 1 < nk;
-                ld_a(cur, 0, fa);
-                ld_b(cur, 0, fb);
-                ld_b(cur, 1, fb1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) { stage_ah(cur ^ 1, t + 1, 0); stage_bh(cur ^ 1, t + 1, 0); stage_bh(cur ^ 1, t + 1, 1); }
-                // A_h1(t) (read in phase B); newer: the 6 pieces just issued
-                if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 0, fa, fb);
-                QUAD(0, 1, fa, fb1);
-                RAW_BARRIER();
-                ld_a(cur, 1, fa);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) { stage_ah(cur ^ 1, t + 1, 1); asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(1, 1, fa, fb1);
-                QUAD(1, 0, fa, fb);
-                RAW_BARRIER();
-            }
-        } else if constexpr (SCH == 3) {
-            // LOAD-part-only balanced schedule: fb/fb1 resident (phase 3 reads nothing), two DMA pieces per phase:
-            //   phase 0: A_h0(t+1), 1: B_h0(t+1), 2: B_h1(t+1), 3: A_h1(t+1); reads/pieces = 12/2, 4/2, 8/2, 0/2.
-            for (int t = 0; t < nk; ++t) {
-                const int cur = t & 1;
-                const bool more = t + 1 < nk;
-                ld_a(cur, 0, fa);
-                ld_b(cur, 0, fb);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) stage_ah(cur ^ 1, t + 1, 0);
-                if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 0, fa, fb);
-                RAW_BARRIER();
-                ld_b(cur, 1, fb1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) stage_bh(cur ^ 1, t + 1, 0);
-                if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 1, fa, fb1);
-                RAW_BARRIER();
-                ld_a(cur, 1, fa);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) stage_bh(cur ^ 1, t + 1, 1);
-                RAW_BARRIER();
-                QUAD(1, 1, fa, fb1);
-                RAW_BARRIER();
-                if (more) { stage_ah(cur ^ 1, t + 1, 1); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-                RAW_BARRIER();
-                QUAD(1, 0, fa, fb);
-                RAW_BARRIER();
-            }
-        } else if constexpr (SCH == 2 || SCH == 4) {
-            // Rebalanced counted schedule.  Both nh fragments of B stay in registers (fb, fb1), so phase 3 reads nothing
-            // from LDS (24 instead of 28 ds_read_b128 per wave per K-tile, and the WAR argument in the header holds
-            // literally); that read-free phase issues the 4 DMA pieces of A_h0,B_h0 of tile t+2 into the buffer tile t
-            // vacated one phase earlier, phase 0 (12 reads) issues none, phases 1 / 2 issue B_h1 / A_h1 of tile t+1:
-            //   ds_read / DMA pieces per phase = 12/0, 4/2, 8/2, 0/4; every half-tile still has 4 phases to land.
-            // In each LOAD part the ds_reads go first and the DMA pieces last, so a wave that queues behind its row's
-            // other waves at the texture-address unit does so with its LDS reads already in flight.
-            for (int t = 0; t < nk; ++t) {
-                const int cur = t & 1;
-                const bool more = t + 1 < nk, more2 = t + 2 < nk;
-                // ---- phase 0: quadrant (0,0) ----
-                ld_a(cur, 0, fa);
-                ld_b(cur, 0, fb);
-                // B_h1(t) (read in phase 1) must have landed; newer: A_h1(t), [A_h0,B_h0](t+1)
-                if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 0, fa, fb);
-                RAW_BARRIER();
-                // ---- phase 1: quadrant (0,1) ----
-                ld_b(cur, 1, fb1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) stage_bh(cur ^ 1, t + 1, 1);
-                // A_h1(t) (phase 2); newer: [A_h0,B_h0](t+1), B_h1(t+1)
-                if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 1, fa, fb1);
-                RAW_BARRIER();
-                // ---- phase 2: quadrant (1,1) ----
-                ld_a(cur, 1, fa);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) stage_ah(cur ^ 1, t + 1, 1);
-                RAW_BARRIER();
-                QUAD(1, 1, fa, fb1);
-                RAW_BARRIER();
-                // ---- phase 3: quadrant (1,0), no LDS reads; first half of tile t+2 into the buffer of tile t ----
-                // (every read of tile t was retired by the lgkmcnt(0) of phase 2's cluster, one barrier ago on this row,
-                //  and the other row's issue point is one barrier later still)
-                RAW_BARRIER();
-                if constexpr (SCH == 2) {
-                    if (more2) { stage_ah(cur, t + 2, 0); stage_bh(cur, t + 2, 0); }
-                    QUAD(1, 0, fa, fb);
-                } else {  // SCH 4: one DMA piece in the shadow of each k-step's first MFMA
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int ks = 0; ks < ((OTTER_DIAG & 2) ? 0 : 4); ++ks) {
-                        acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks], fa[0][ks], acc[2][0], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (more2) { if (ks < 2) stage_ah(cur, t + 2, 0, ks, ks + 1); else stage_bh(cur, t + 2, 0, ks - 2, ks - 1); }
-                        __builtin_amdgcn_sched_barrier(0);
-                        acc[3][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks], fa[1][ks], acc[3][0], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_s_setprio(0);
-                }
-                // [A_h0,B_h0](t+1) (next phase 0); newer: B_h1(t+1), A_h1(t+1), [A_h0,B_h0](t+2)
-                if (more2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                RAW_BARRIER();
-            }
-        } else if constexpr (CNT) {
-            for (int t = 0; t < nk; ++t) {
-                const int cur = t & 1;
-                const bool more = t + 1 < nk;
-                // ---- phase 0: quadrant (0,0) ----
-                if (more) { stage_ah(cur ^ 1, t + 1, 0); stage_bh(cur ^ 1, t + 1, 0); }
-                ld_a(cur, 0, fa);
-                ld_b(cur, 0, fb);
-                // rows read in phase 1 (B_h1 of this tile) must have landed before the barrier after the next cluster
-                if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                RAW_BARRIER();
-                QUAD(0, 0, fa, fb);
-                RAW_BARRIER();
-                // ---- phase 1: quadrant (0,1) ----
-                if (more) stage_bh(cur ^ 1, t + 1, 1);
-                ld_b(cur, 1, fb);
-                if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // A_h1 of this tile (phase 2)
-                RAW_BARRIER();
-                QUAD(0, 1, fa, fb);
-                RAW_BARRIER();
-                // ---- phase 2: quadrant (1,1) ----
-                if (more) stage_ah(cur ^ 1, t + 1, 1);
-                ld_a(cur, 1, fa);
-                RAW_BARRIER();
-                QUAD(1, 1, fa, fb);
-                RAW_BARRIER();
-                // ---- phase 3: quadrant (1,0) ----
-                ld_b(cur, 0, fb);
-                if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // A_h0, B_h0 of the next tile (its phase 0)
-                RAW_BARRIER();
-                QUAD(1, 0, fa, fb);
-                RAW_BARRIER();
-            }
-        } else
+        bf16x8_t fa[2][4], fb[4], fb1[4];
+        // LOAD-part-only balanced schedule: fb/fb1 resident (phase 3 reads nothing), two DMA pieces per phase:
+        //   phase 0: A_h0(t+1), 1: B_h0(t+1), 2: B_h1(t+1), 3: A_h1(t+1); reads/pieces = 12/2, 4/2, 8/2, 0/2.
         for (int t = 0; t < nk; ++t) {
             const int cur = t & 1;
-            // ---- phase 0: quadrant (0,0) ----
+            const bool more = t + 1 < nk;
             ld_a(cur, 0, fa);
             ld_b(cur, 0, fb);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) stage_ah(cur ^ 1, t + 1, 0);
+            if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             RAW_BARRIER();
             QUAD(0, 0, fa, fb);
-            // the next tile's DMA is issued AFTER this cluster: by now the other wave row has retired its last reads of
-            // the buffer being refilled (its phase-3 reads complete before its own phase-3 MFMAs, one barrier ago)
-            if (t + 1 < nk) stage(cur ^ 1, t + 1);
             RAW_BARRIER();
-            // ---- phase 1: quadrant (0,1) ----
-            ld_b(cur, 1, fb);
+            ld_b(cur, 1, fb1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) stage_bh(cur ^ 1, t + 1, 0);
+            if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             RAW_BARRIER();
-            QUAD(0, 1, fa, fb);
+            QUAD(0, 1, fa, fb1);
             RAW_BARRIER();
-            // ---- phase 2: quadrant (1,1) ----
             ld_a(cur, 1, fa);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) stage_bh(cur ^ 1, t + 1, 1);
             RAW_BARRIER();
-            QUAD(1, 1, fa, fb);
+            QUAD(1, 1, fa, fb1);
             RAW_BARRIER();
-            // ---- phase 3: quadrant (1,0); retire this wave's share of the next tile's DMA before the barrier ----
-            ld_b(cur, 0, fb);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (more) { stage_ah(cur ^ 1, t + 1, 1); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
             RAW_BARRIER();
             QUAD(1, 0, fa, fb);
             RAW_BARRIER();
@@ -1444,31 +1149,17 @@ __global__ __launch_bounds__(512) void gemm_bf16_ph_kernel(GemmArgs g) {
         float* blk = reinterpret_cast<float*>(smem) + wave * (32 * EPI_LD);
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
-            if constexpr ((OTTER_DIAG & 16) != 0) {
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) part += acc[mi][ni][r];
-                continue;
-            }
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) park_block(blk, acc[mi][ni], lane, ni * 32);
             __builtin_amdgcn_wave_barrier();
             part += epilogue_stripe<EPI>(g, sgate, blk, m0 + wr * 128 + mi * 32, n0 + wc * 64, lane);
             __builtin_amdgcn_wave_barrier();
         }
-        if constexpr ((OTTER_DIAG & 20) != 0) {  // keep `part` (hence the accumulators) observable
-            if (part == 12345.678f) reinterpret_cast<float*>(g.C)[threadIdx.x] = part;
-        }
         block_partial<8, EPI>(g, part, reinterpret_cast<float*>(smem), vb);
         __syncthreads();
     }
 #undef RAW_BARRIER
 }
-
-#ifdef OTTER_EXPERIMENTAL  // tools-only: variants 4/5/12 (multi-stage ring), 17, 18-23 (one wave per SIMD, register-resident K-tile on 32x32x16): the round-1/2 generations that led to variant 26
-#include "experimental/gemm_generations_r1_r2.inc"
-#endif
 
 // ------------------------------------------------------------------------------------------------------------
 // bf16 register-resident K-tile kernel on v_mfma_f32_16x16x32_bf16 (variant 26): variant 18's pipeline, LDS image and DMA
@@ -1525,16 +1216,13 @@ __device__ __forceinline__ void gemm_dma16_asm(u32x4_t r, unsigned lds, uint32_t
 // global address: the per-lane source offset of piece q is stored 1024 q low.  tools/probe/dma_issue.hip: an `s_mov m0 + s_nop` pair beside
 // back-to-back MFMAs costs ~12 cycles of matrix pipe; 12 of the 16 pairs of a K-tile go (profiles/r06d_dma_issue_probe.txt: +6 % MFMA rate on zeros,
 // +3-4 % on random operands).  Nothing else in these kernels touches M0 (checked in the object code: 128 s_mov m0 = 128 LDS-DMA instructions).
-#ifndef OTTER_T4_DMA_AUX   // cache-policy bits of the operand loads (A/B builds: " nt", " sc1", " sc0 sc1"); default: none
-#define OTTER_T4_DMA_AUX ""
-#endif
 template <int Q>
 __device__ __forceinline__ void gemm_dma16_asm_q(u32x4_t r, unsigned lds_group, uint32_t voff_low, uint32_t soff) {
-    if constexpr (Q == 0) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" OTTER_T4_DMA_AUX " lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
-    else if constexpr (Q == 4) asm volatile("buffer_load_dwordx4 %1, %2, %3 offen" OTTER_T4_DMA_AUX " lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");   // M0 written a slot earlier
-    else if constexpr (Q == 1) asm volatile("buffer_load_dwordx4 %1, %2, %3 offen offset:1024" OTTER_T4_DMA_AUX " lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
-    else if constexpr (Q == 2) asm volatile("buffer_load_dwordx4 %1, %2, %3 offen offset:2048" OTTER_T4_DMA_AUX " lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
-    else asm volatile("buffer_load_dwordx4 %1, %2, %3 offen offset:3072" OTTER_T4_DMA_AUX " lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
+    if constexpr (Q == 0) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
+    else if constexpr (Q == 4) asm volatile("buffer_load_dwordx4 %1, %2, %3 offen lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");   // M0 written a slot earlier
+    else if constexpr (Q == 1) asm volatile("buffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
+    else if constexpr (Q == 2) asm volatile("buffer_load_dwordx4 %1, %2, %3 offen offset:2048 lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
+    else asm volatile("buffer_load_dwordx4 %1, %2, %3 offen offset:3072 lds" : : "s"(lds_group), "v"(voff_low), "s"(r), "s"(soff) : "memory");
 }
 
 // Address of a transpose read: k-row, half row, swizzled block and the lane's 8 bytes occupy DISJOINT bit fields of the LDS
@@ -1645,11 +1333,8 @@ __device__ __forceinline__ bf16x8_t ldf_tr_rt(unsigned lane_const, int koff, int
 #define ACC_IRP_5 "160,161,162,163,164,165,166,167,168,169,170,171,172,173,174,175,176,177,178,179,180,181,182,183,184,185,186,187,188,189,190,191"
 #define ACC_IRP_6 "192,193,194,195,196,197,198,199,200,201,202,203,204,205,206,207,208,209,210,211,212,213,214,215,216,217,218,219,220,221,222,223"
 #define ACC_IRP_7 "224,225,226,227,228,229,230,231,232,233,234,235,236,237,238,239,240,241,242,243,244,245,246,247,248,249,250,251,252,253,254,255"
-#ifndef OTTER_KMDBG
-#define OTTER_KMDBG 0   // debug builds only (python -m otter_amd.build --define OTTER_KMDBG=n sfx): 1 = builtin MFMA, 2 = builtin LDS-DMA
-#endif
 // XT (round 6, variant 31): the DMA ring keeps running ACROSS the tiles of a persistent workgroup -- see the block comment at T4_XT_* below.
-template <int EPI, int SCH, bool TA = false, bool TB = false, bool XT = false>
+template <int EPI, bool TA = false, bool TB = false, bool XT = false>
 __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
     constexpr int BM = 256, BN = 256, NT = 256;
     constexpr int TILE = (BM + BN) * 128;  // 64 KB: [256 A rows ; 256 B rows] x 128 B  (K-major operand: [64 k][256 m] x 2 B, same 32 KB)
@@ -1756,7 +1441,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
     int kx_t = 0;                 // K-major schedule: wrapped index and scalar source offsets of the K-tile in flight (T4_SETKX)
     uint32_t kx_a = 0, kx_b = 0;
     static_assert(!XT || (!TA && !TB), "the cross-tile form is built for K-contiguous operands only (its K-tile offsets come from the T4_SETK slots of KTILE_T0)");
-    constexpr bool M0G = XT && !TA && !TB && (OTTER_T4_M0GROUP != 0);   // M0 written once per four pieces (gemm_dma16_asm_q)
     // (m0_set: the schedule wrote this group's M0 one slot earlier through dma_m0() -- KTILE_T0's in-loop pieces; the prologue's calls write it themselves)
     auto dma = [&](int bufv, int kt, int p, bool m0_set = false) {
         if constexpr ((OTTER_T4_ABL & 1) != 0) { if (kt >= 2) return; }   // ablation build: no LDS-DMA inside the K loop (timing only, wrong results)
@@ -1765,13 +1449,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
             kt += krot_plain;
             if (kt >= nk) kt -= nk;
         }
-        if constexpr (XT && M0G) {   // grouped M0 (see gemm_dma16_asm_q): wave w fills the 1 KB chunks 8 w .. 8 w + 7 of each operand's 32 KB, piece by piece
+        if constexpr (XT) {   // asm issue, grouped M0 (see gemm_dma16_asm_q): wave w fills the 1 KB chunks 8 w .. 8 w + 7 of each operand's 32 KB, piece by piece
             const unsigned grp = smem_lds + (unsigned)((bufv & 1) * TILE + (p >> 3) * (BM * 128) + (wave * 8 + (p & 4)) * 1024);
             const uint32_t vo = p < 8 ? oa[p & 7] : ob[p & 7];
             const uint32_t so = p < 8 ? sa_k : sb_k;
             switch (p & 3) {
                 case 0:
-                    if (m0_set && (OTTER_T4_M0EARLY != 0)) { if (p < 8) gemm_dma16_asm_q<4>(rs4_a, grp, vo, so); else gemm_dma16_asm_q<4>(rs4_b, grp, vo, so); }
+                    if (m0_set) { if (p < 8) gemm_dma16_asm_q<4>(rs4_a, grp, vo, so); else gemm_dma16_asm_q<4>(rs4_b, grp, vo, so); }
                     else { if (p < 8) gemm_dma16_asm_q<0>(rs4_a, grp, vo, so); else gemm_dma16_asm_q<0>(rs4_b, grp, vo, so); }
                     break;
                 case 1: if (p < 8) gemm_dma16_asm_q<1>(rs4_a, grp, vo, so); else gemm_dma16_asm_q<1>(rs4_b, grp, vo, so); break;
@@ -1780,16 +1464,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
             }
             return;
         }
-        if constexpr (XT) {   // asm issue for every instantiation: invisible to hipcc's wait-count pass, counted by the schedule's own s_waitcnt
-            const unsigned dst = smem_lds + (unsigned)wbase;
-            if (p < 8) gemm_dma16_asm(rs4_a, dst, oa[TA ? (p & 1) : (p & 7)], TA ? sa_k + (uint32_t)((p & 7) >> 1) * ksa : sa_k);
-            else gemm_dma16_asm(rs4_b, dst, ob[TB ? (p & 1) : (p & 7)], TB ? sb_k + (uint32_t)((p & 7) >> 1) * ksb : sb_k);
-            return;
-        }
         // K-major operand: piece i = k-rows 8 i + (tid >> 5); pieces i and i + 2 differ by 16 rows = a UNIFORM byte offset, and the
         // swizzle of a row depends on i only through its parity -- two per-lane offsets (even / odd pieces) instead of eight, the rest
         // rides in the scalar offset (the register file of this kernel is full: 256 accumulators + 128 fragment registers)
-        if constexpr ((TA || TB) && !(OTTER_KMDBG & 2)) {   // asm issue for BOTH operands of a K-major instantiation (see gemm_dma16_asm)
+        if constexpr (TA || TB) {   // asm issue for BOTH operands of a K-major instantiation (see gemm_dma16_asm)
             const unsigned dst = smem_lds + (unsigned)wbase;
             if (m0_set) {   // (KTILE_X0 since round 6d: dma_m0x() wrote this piece's M0 one slot earlier and T4_SETKX the K-tile's scalar offsets; the
                             //  prologue's calls do both themselves)
@@ -1802,31 +1480,31 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
                 }
             } else
             if (p < 8) {
-                if constexpr (TA) gemm_dma16_asm(rs4_a, dst, oa[p & 1], (uint32_t)(4 * kt + ((p & 7) >> 1)) * ksa);   // (OTTER_KMDBG: debug builds)
+                if constexpr (TA) gemm_dma16_asm(rs4_a, dst, oa[p & 1], (uint32_t)(4 * kt + ((p & 7) >> 1)) * ksa);
                 else gemm_dma16_asm(rs4_a, dst, oa[p & 7], (uint32_t)kt * ksa);
             } else {
                 if constexpr (TB) gemm_dma16_asm(rs4_b, dst, ob[p & 1], (uint32_t)(4 * kt + ((p & 7) >> 1)) * ksb);
                 else gemm_dma16_asm(rs4_b, dst, ob[p & 7], (uint32_t)kt * ksb);
             }
-        } else if (p < 8) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(smem + wbase), 16, (int)oa[TA ? (p & 1) : (p & 7)],
-                                                     (int)((TA ? (uint32_t)(4 * kt + ((p & 7) >> 1)) : (uint32_t)kt) * ksa), 0, 0);
+        } else if (p < 8) {   // K-contiguous operands, plain form: the builtin
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (__attribute__((address_space(3))) void*)(smem + wbase), 16, (int)oa[p & 7],
+                                                     (int)((uint32_t)kt * ksa), 0, 0);
         } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(smem + wbase), 16, (int)ob[TB ? (p & 1) : (p & 7)],
-                                                     (int)((TB ? (uint32_t)(4 * kt + ((p & 7) >> 1)) : (uint32_t)kt) * ksb), 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (__attribute__((address_space(3))) void*)(smem + wbase), 16, (int)ob[p & 7],
+                                                     (int)((uint32_t)kt * ksb), 0, 0);
         }
     };
     // the M0 of the group of four pieces that starts with piece p (p = 0, 4, 8, 12), written by the schedule one MFMA slot before that piece: the
     // s_mov's latency then hides under the MFMA instead of standing in front of the buffer_load (tools/probe/dma_issue.hip: -40 cycles per K-tile)
     auto dma_m0x = [&](int bufv, int p) {   // K-major schedule (KTILE_X0): the M0 of piece p, one MFMA slot before the piece
-        if constexpr ((TA || TB) && !(OTTER_KMDBG & 2)) {
+        if constexpr (TA || TB) {
             const unsigned dst = smem_lds + (unsigned)((bufv & 1) * TILE + (p >> 3) * (BM * 128) + ((p & 7) * NT + wave * 64) * 16);
             asm volatile("s_mov_b32 m0, %0" : : "s"(dst) : "memory");
         }
     };
     auto dma_m0 = [&](int bufv, int p) {
         if constexpr ((OTTER_T4_ABL & 1) != 0) return;
-        if constexpr (XT && M0G && (OTTER_T4_M0EARLY != 0)) {
+        if constexpr (XT) {
             const unsigned grp = smem_lds + (unsigned)((bufv & 1) * TILE + (p >> 3) * (BM * 128) + (wave * 8 + (p & 4)) * 1024);
             asm volatile("s_mov_b32 m0, %0" : : "s"(grp) : "memory");
         }
@@ -1898,15 +1576,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
         for (int i = 0; i < 8; ++i) {
             // (grouped M0: piece i of a wave is the 1 KB chunk 8 wave + i of the operand's LDS image -- rows 64 wave + 8 i .. + 7 -- and its source offset
             //  is stored 1024 (i & 3) low: the instruction's immediate offset puts it back.  Rows >= 8 lie >= 8 row pitches >= 4 KB up: no underflow.)
-            const int c = M0G ? (wave * 8 + i) * 64 + lane : i * NT + tid, row = c >> 3, phys = c & 7;
+            const int c = (wave * 8 + i) * 64 + lane, row = c >> 3, phys = c & 7;
             const int slot = phys ^ ((row >> 1) & 7);
-            const int krow = c >> 5, c16 = c & 31;
-            const int mlog = ((((c16 >> 1) ^ ((krow & 3) | (((krow >> 3) & 1) << 2))) << 1) | (c16 & 1)) * 8;
-            const uint32_t low = M0G ? (uint32_t)(i & 3) * 1024u : 0u;
-            if constexpr (TA) { if (i < 2) oa[i] = ((uint32_t)krow * (uint32_t)g.lda + (uint32_t)mlog) * 2u; }
-            else oa[i] = ((uint32_t)row * (uint32_t)g.lda + (uint32_t)(slot * 8)) * 2u - low;
-            if constexpr (TB) { if (i < 2) ob[i] = ((uint32_t)krow * (uint32_t)g.ldb + (uint32_t)mlog) * 2u; }
-            else ob[i] = ((uint32_t)row * (uint32_t)g.ldb + (uint32_t)(slot * 8)) * 2u - low;
+            const uint32_t low = (uint32_t)(i & 3) * 1024u;
+            oa[i] = ((uint32_t)row * (uint32_t)g.lda + (uint32_t)(slot * 8)) * 2u - low;
+            ob[i] = ((uint32_t)row * (uint32_t)g.ldb + (uint32_t)(slot * 8)) * 2u - low;
         }
     }
     for (int vb = blockIdx.x; vb < ntiles; vb += gridDim.x) {
@@ -1974,7 +1648,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
         f32x4_t acc[8][8];
         // accumulators in explicit AGPRs (asm MFMAs): the K-major instantiations and EVERY cross-tile instantiation (with the builtin MFMA
         // hipcc re-homes accumulator blocks around the restructured tile loop: hundreds of v_accvgpr_mov at the K loop's entry, spills)
-        constexpr bool XACC = (TA || TB || XT) && !(OTTER_KMDBG & 1);
+        constexpr bool XACC = TA || TB || XT;
         if constexpr (XACC && XT) {
             // nothing: the first K-tile's k-step 0 runs with C = 0 (MMAZ in KTILE_T0F)
         } else if constexpr (XACC) {
@@ -2044,7 +1718,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
 // the scalar source offsets of the K-tile this iteration's DMA pieces fetch, in three pieces on free slots of the schedule (cross-tile form; nothing otherwise)
 #define T4_SETK(N)                                                                                                        \
     do {                                                                                                                  \
-        if constexpr (XT && !(OTTER_T4_SETK_BURST)) {                                                                                               \
+        if constexpr (XT) {                                                                                               \
             if constexpr ((N) == 0) { xs_x = xs_kt + xs_rot; if (xs_x >= nk) xs_x -= nk; }                                \
             else if constexpr ((N) == 1) xs_kp = (xs_x & ~xs_kgm) | ((xs_x + xs_kc) & xs_kgm);                            \
             else {                                                                                                        \
@@ -2068,9 +1742,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
 #define KTILE_T0 KTILE_T0_0
 #define KTILE_T0F KTILE_T0F_0
 #define KTILE_X0 KTILE_X0_0
-#ifdef OTTER_EXPERIMENTAL  // tools-only: variants 27-29: alternative slot placements T1-T3 of variant 26's K-tile schedule (generated by tools/gen/gemm_t4_schedule.py)
-#include "experimental/gemm_t4_placements_t1_t3.inc"
-#endif
 #define KLOOP(KT)                                   \
     do {                                            \
         int t = 0;                                  \
@@ -2085,55 +1756,32 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
 // the buffers the steady state would refill anyway.  Iteration 0 is peeled for its wait: behind a full-tile tail, K-tile 1 is followed in the
 // queue by that tail's >= 32 global accesses, which the count may leave in flight (DMA == 2, see T4_WAIT_NEXT); iteration 1's wait for
 // K-tile 2 is the first that retires them.  Needs nk >= 4 (the host falls back to the plain form below that).
-// (XS_AT: announce the tile / K-tile index for the T4_SETK slots; the A/B build -DOTTER_T4_SETK_BURST=1 computes the offsets in one burst in front of the
-//  K-tile instead, as the kernel did until round 6d)
-#if OTTER_T4_SETK_BURST
-#define XS_TILE(T) ((void)0)
-#define XS_AT(T, K_) xt_setk(T, K_)
-#else
+// (XS_TILE / XS_AT: announce the tile / the K-tile index for the T4_SETK slots)
 #define XS_TILE(T) xs_tile(T)
-#define XS_AT(T, K_) (xs_kt = (K_))
-#endif
+#define XS_AT(K_) (xs_kt = (K_))
 #define KLOOP_XT(KT, KTF)                           \
     do {                                            \
         XS_TILE(xt_cur);                            \
-        XS_AT(xt_cur, 2);                           \
+        XS_AT(2);                           \
         KTF(0, 0, 2, true);                         \
-        XS_AT(xt_cur, 3);                           \
+        XS_AT(3);                           \
         KT(1, 1, true, true);                       \
         int t = 2;                                  \
         for (; t + 2 < nk; t += 2) {                \
-            XS_AT(xt_cur, t + 2);                   \
+            XS_AT(t + 2);                   \
             KT(0, t, true, true);                   \
-            XS_AT(xt_cur, t + 3);                   \
+            XS_AT(t + 3);                   \
             KT(1, t + 1, true, true);               \
         }                                           \
         XS_TILE(xt_nxt);                            \
-        XS_AT(xt_nxt, 0);                           \
+        XS_AT(0);                           \
         KT(0, t, xt_pre, true);                     \
-        XS_AT(xt_nxt, 1);                           \
+        XS_AT(1);                           \
         KT(1, t + 1, xt_pre, false);                \
     } while (0)
-#ifdef OTTER_EXPERIMENTAL
-        static_assert(!XT || SCH == 0, "the cross-tile form runs the default placement only");
-        if constexpr (XT) {
-            if constexpr (TA || TB) KLOOP_XT(KTILE_X0, KTILE_X0);
-            else KLOOP_XT(KTILE_T0, KTILE_T0F);
-        } else if constexpr (SCH == 0) KLOOP(KTILE_T0);
-        else if constexpr (SCH == 1) KLOOP(KTILE_T1);
-        else if constexpr (SCH == 2) KLOOP(KTILE_T2);
-        else KLOOP(KTILE_T3);
-#undef KTILE_T1
-#undef KTILE_T2
-#undef KTILE_T3
-#else
-        static_assert(SCH == 0, "the alternative placements of variant 26 (27-29) are in the OTTER_EXPERIMENTAL build only");
-        if constexpr (XT) {
-            if constexpr ((TA || TB) && !(OTTER_KMDBG & 4)) KLOOP_XT(KTILE_X0, KTILE_X0);
-            else KLOOP_XT(KTILE_T0, KTILE_T0F);
-        } else if constexpr ((TA || TB) && !(OTTER_KMDBG & 4)) KLOOP(KTILE_X0);
+        if constexpr (XT) KLOOP_XT(KTILE_T0, KTILE_T0F);
+        else if constexpr (TA || TB) KLOOP(KTILE_X0);
         else KLOOP(KTILE_T0);
-#endif
 #if (OTTER_T4_ABL & 4)
 #undef __builtin_amdgcn_s_barrier
 #endif
@@ -2225,6 +1873,17 @@ __global__ __launch_bounds__(256) void gemm_bf16_t4_kernel(GemmArgs g) {
 #undef SB
 #undef TMARK
 }
+#undef ACC_ZERO_ROW
+#undef ACC_IRP_0
+#undef ACC_IRP_1
+#undef ACC_IRP_2
+#undef ACC_IRP_3
+#undef ACC_IRP_4
+#undef ACC_IRP_5
+#undef ACC_IRP_6
+#undef ACC_IRP_7
+#undef AC_ROW
+// (AC_<mi>_<ni>, the 64 register-name lists, stay defined to the end of the translation unit: they hold no schedule)
 
 // ------------------------------------------------------------------------------------------------------------
 // bf16 small-grid kernel (variant 25): 128x128 tile, 4 waves of 64x64, BK = 64 stages in a 4-deep LDS-DMA ring.
@@ -2680,27 +2339,25 @@ int t4_korder() {
     if (dflt < 0) { const char* e = getenv("OTTER_GEMM_KORDER"); dflt = e ? (atoi(e) & 127) : OTTER_T4_KORDER_DEFAULT; }
     return g_korder_force >= 0 ? g_korder_force : dflt;
 }
-enum Cfg { CFG_128 = 1, CFG_256 = 2, CFG_256_GLDS = 3, CFG_MS4 = 4, CFG_MS5 = 5, CFG_PH = 6, CFG_PHC = 7, CFG_WS = 8, CFG_PHB = 9, CFG_PHCB = 10, CFG_PHRB = 11, CFG_MS5B = 12, CFG_PHLB = 13, CFG_PHIB = 14, CFG_PH2B = 15, CFG_PHDB = 16, CFG_Q4 = 17, CFG_R4 = 18, CFG_R4B = 19, CFG_R4C = 20, CFG_R4P = 21, CFG_R4M = 22, CFG_R4N = 23, CFG_S4 = 25, CFG_T4 = 26, CFG_T4B = 27, CFG_T4C = 28, CFG_T4M = 29, CFG_S4H = 30, CFG_F32 = 100 };
+// The numbers are public (otter_gemm_set_variant; bench.py and the tests pass them).  4-12, 14-23 and 27-29 were the kernel generations and
+// schedule placements that led to 13 and 26: retired, DESIGN_HISTORY.md names the last commit that holds them.
+enum Cfg { CFG_128 = 1, CFG_256 = 2, CFG_256_GLDS = 3, CFG_PHLB = 13, CFG_S4 = 25, CFG_T4 = 26, CFG_S4H = 30, CFG_F32 = 100 };
 
 // wide: an operand spans >= 4 GB, so the kernels that address it with 32-bit byte offsets are out
 int pick_cfg(int64_t M, int64_t N, int64_t K, int ab_dtype, bool wide = false) {
     if (ab_dtype == OTTER_F32) return CFG_F32;
     int v = g_variant;
     if (v == 0) {
-        // interleaved A/B medians on MI355X (tools/gemm_ab.py): round 2's one-wave-per-SIMD kernel with the
-        // register-resident K-tile (variant 18) beats round 1's balanced 8-wave phased schedule (variant 13) on all three
-        // FFN shapes (1.29 / 1.49 / 1.43 PF vs 1.19 / 1.39 / 1.37 on one box); it needs K % 128 == 0, else 13 stays
+        // interleaved A/B medians on MI355X (tools/gemm_ab.py): the one-wave-per-SIMD kernel with the register-resident
+        // K-tile (variant 26) beats the balanced 8-wave phased schedule (variant 13) on all three FFN shapes; it needs K % 128 == 0,
+        // else 13 stays
         if (cdiv64(M, 256) * cdiv64(N, 256) >= 192) v = (K % 128 == 0 && !wide) ? CFG_T4 : CFG_PHLB;
         else if (K % 256 == 0 && K >= 512 && !wide && cdiv64(M, 128) * cdiv64(N, 128) <= 512) v = CFG_S4;   // few tiles, long reduction: the ring
         else v = CFG_128;
     }
-    if ((v == CFG_MS4 || v == CFG_MS5 || v == CFG_MS5B) && (K % 32 != 0)) v = CFG_256_GLDS;
-    if (v == CFG_WS && K % 64 != 0) v = CFG_256;
-    const bool ph = v == CFG_PH || v == CFG_PHC || v == CFG_PHB || v == CFG_PHCB || v == CFG_PHRB || v == CFG_PHLB || v == CFG_PHIB || v == CFG_PH2B || v == CFG_PHDB;
-    if (ph && (K % 64 != 0 || wide)) v = (K % 64 == 0) ? CFG_256_GLDS : CFG_256;
-    if ((v == CFG_Q4 || v == CFG_R4 || v == CFG_R4B || v == CFG_R4C || v == CFG_R4P || v == CFG_R4M || v == CFG_R4N || v == CFG_T4 || v == CFG_T4B || v == CFG_T4C || v == CFG_T4M) && (K % 128 != 0 || wide)) v = (K % 64 == 0 && !wide) ? CFG_PHLB : ((K % 64 == 0) ? CFG_256_GLDS : CFG_256);
+    if (v == CFG_PHLB && (K % 64 != 0 || wide)) v = (K % 64 == 0) ? CFG_256_GLDS : CFG_256;
+    if (v == CFG_T4 && (K % 128 != 0 || wide)) v = (K % 64 == 0 && !wide) ? CFG_PHLB : ((K % 64 == 0) ? CFG_256_GLDS : CFG_256);
     if ((v == CFG_S4 || v == CFG_S4H) && (K % 256 != 0 || wide)) v = CFG_128;
-    if (v == CFG_MS5B && wide) v = CFG_MS5;
     if (v == CFG_256_GLDS && (K % 64 != 0)) v = CFG_256;
     return v;
 }
@@ -2742,28 +2399,25 @@ struct Prof {
     unsigned char* kmajor = nullptr;   // per event: the launch had a K-major operand
 } g_prof;
 
-template <typename KernelT>
-int set_smem(KernelT kernel, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) OTTER_FAIL(OTTER_ERR_LAUNCH, "hipFuncSetAttribute(%d B LDS): %s", bytes, hipGetErrorString(e));
+// Launch of a kernel with dynamic LDS: the attribute that admits more than 64 KB is set once per kernel instantiation (the function-local
+// static of this template, which is keyed on the kernel).
+template <auto Kernel>
+int launch_lds(unsigned blocks, unsigned threads, int smem, hipStream_t st, const GemmArgs& g) {
+    static bool once = false;
+    if (!once) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) OTTER_FAIL(OTTER_ERR_LAUNCH, "hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
+        once = true;
+    }
+    hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(threads), smem, st, g);
     return OTTER_OK;
 }
 
+// variants 1-3.  Persistent grid: one resident wave of blocks (two per CU of the 128^2 tile, one of the 256^2 tile), or one per tile if fewer
 template <int BM, int BN, int WM, int WN, bool GLDS, int EPI>
-int launch_one(dim3 grid, hipStream_t st, const GemmArgs& g) {
-    static bool once = false;
-    const int smem = 2 * (BM + BN) * 128;
-    if (!once) {
-        int rc = set_smem(gemm_bf16_kernel<BM, BN, WM, WN, GLDS, EPI>, smem);
-        if (rc) return rc;
-        once = true;
-    }
-    // persistent grid: one resident wave of blocks (256 CUs x blocks that fit per CU), rounded to a multiple of 8
-    const unsigned per_cu = (BM == 256) ? 1u : 2u;
-    unsigned pg = persistent_cus() * per_cu;
-    if (grid.x < pg) pg = grid.x;
-    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, GLDS, EPI>), dim3(pg), dim3(WM * WN * 64), smem, st, g);
-    return OTTER_OK;
+int launch_tiled(unsigned tiles, hipStream_t st, const GemmArgs& g) {
+    const unsigned pg = persistent_cus() * ((BM == 256) ? 1u : 2u);
+    return launch_lds<gemm_bf16_kernel<BM, BN, WM, WN, GLDS, EPI>>(tiles < pg ? tiles : pg, WM * WN * 64, 2 * (BM + BN) * 128, st, g);
 }
 
 template <int EPI>
@@ -2772,157 +2426,31 @@ int launch_epi(int cfg, dim3 grid, hipStream_t st, const GemmArgs& g) {
         hipLaunchKernelGGL(gemm_f32_kernel<EPI>, grid, dim3(256), 0, st, g);
         return OTTER_OK;
     }
-    if (cfg == CFG_128) return launch_one<128, 128, 2, 2, false, EPI>(grid, st, g);
-    if (cfg == CFG_256) return launch_one<256, 256, 2, 4, false, EPI>(grid, st, g);
-#ifdef OTTER_EXPERIMENTAL
-    if (cfg == CFG_WS) {
-        static bool once = false;
-        const int smem = 2 * (256 + 256) * 128;
-        if (!once) { int rc = set_smem(gemm_bf16_ws_kernel<EPI>, smem); if (rc) return rc; once = true; }
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
-        hipLaunchKernelGGL((gemm_bf16_ws_kernel<EPI>), dim3(pg), dim3(768), smem, st, g);
-        return OTTER_OK;
-    }
-#endif
-    if (cfg == CFG_PH || cfg == CFG_PHC || cfg == CFG_PHB || cfg == CFG_PHCB || cfg == CFG_PHRB || cfg == CFG_PHLB || cfg == CFG_PHIB || cfg == CFG_PH2B || cfg == CFG_PHDB) {
-        const int smem = 2 * (256 + 256) * 128;
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
-#define LAUNCH_PH(CNT_, BUF_)                                                                                              \
-    do {                                                                                                                   \
-        static bool once = false;                                                                                          \
-        if (!once) { int rc = set_smem(gemm_bf16_ph_kernel<EPI, CNT_, BUF_>, smem); if (rc) return rc; once = true; }      \
-        hipLaunchKernelGGL((gemm_bf16_ph_kernel<EPI, CNT_, BUF_>), dim3(pg), dim3(512), smem, st, g);                      \
-    } while (0)
-#ifdef OTTER_EXPERIMENTAL
-        if (cfg == CFG_PH) LAUNCH_PH(0, false);
-        else if (cfg == CFG_PHC) LAUNCH_PH(1, false);
-        else if (cfg == CFG_PHB) LAUNCH_PH(0, true);
-        else if (cfg == CFG_PHCB) LAUNCH_PH(1, true);
-        else if (cfg == CFG_PHRB) LAUNCH_PH(2, true);
-        else if (cfg == CFG_PHLB) LAUNCH_PH(3, true);
-        else if (cfg == CFG_PHIB) LAUNCH_PH(4, true);
-        else if (cfg == CFG_PH2B) LAUNCH_PH(5, true);
-        else LAUNCH_PH(6, true);
-#else
-        LAUNCH_PH(3, true);   // variant 13, the only phased schedule of the product build (pick_cfg admits no other)
-#endif
-#undef LAUNCH_PH
-        return OTTER_OK;
-    }
-#ifdef OTTER_EXPERIMENTAL
-    if (cfg == CFG_MS4 || cfg == CFG_MS5 || cfg == CFG_MS5B) {
-        const int smem = (cfg == CFG_MS4 ? 4 : 5) * 32768;
-#define LAUNCH_MS(NS_, BUF_)                                                                                               \
-    do {                                                                                                                   \
-        static bool once = false;                                                                                          \
-        if (!once) { int rc = set_smem(gemm_bf16_ms_kernel<NS_, EPI, BUF_>, smem); if (rc) return rc; once = true; }       \
-        hipLaunchKernelGGL((gemm_bf16_ms_kernel<NS_, EPI, BUF_>), grid, dim3(256), smem, st, g);                           \
-    } while (0)
-        if (cfg == CFG_MS4) LAUNCH_MS(4, false);
-        else if (cfg == CFG_MS5) LAUNCH_MS(5, false);
-        else LAUNCH_MS(5, true);
-#undef LAUNCH_MS
-        return OTTER_OK;
-    }
-    if (cfg == CFG_R4 || cfg == CFG_R4B || cfg == CFG_R4C || cfg == CFG_R4P || cfg == CFG_R4M || cfg == CFG_R4N) {
-        const int smem = TAIL_LDS_BYTES > 2 * 65536 ? TAIL_LDS_BYTES : 2 * 65536;  // two K-tile buffers; the tail's parking buffers alias them
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
-#define LAUNCH_R4(SCH_, PF_)                                                                                               \
-    do {                                                                                                                   \
-        static bool once = false;                                                                                          \
-        if (!once) { int rc = set_smem(gemm_bf16_r4_kernel<EPI, SCH_, PF_>, smem); if (rc) return rc; once = true; }       \
-        hipLaunchKernelGGL((gemm_bf16_r4_kernel<EPI, SCH_, PF_>), dim3(pg), dim3(256), smem, st, g);                       \
-    } while (0)
-        if (cfg == CFG_R4) LAUNCH_R4(0, false);
-        else if (cfg == CFG_R4B) LAUNCH_R4(1, false);
-        else if (cfg == CFG_R4C) LAUNCH_R4(2, false);
-        else if (cfg == CFG_R4M) LAUNCH_R4(3, false);
-        else if (cfg == CFG_R4N) LAUNCH_R4(4, false);
-        else LAUNCH_R4(0, true);
-#undef LAUNCH_R4
-        return OTTER_OK;
-    }
-#endif
-    if (cfg == CFG_T4 || cfg == CFG_T4B || cfg == CFG_T4C || cfg == CFG_T4M) {
-        const int smem = TAIL_LDS_BYTES > 2 * 65536 ? TAIL_LDS_BYTES : 2 * 65536;
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
+    if (cfg == CFG_128) return launch_tiled<128, 128, 2, 2, false, EPI>(grid.x, st, g);
+    if (cfg == CFG_256) return launch_tiled<256, 256, 2, 4, false, EPI>(grid.x, st, g);
+    // the persistent kernels: one workgroup per CU left to the GEMMs (otter_gemm_set_cu_budget), or one per tile if fewer
+    const unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
+    if (cfg == CFG_PHLB) return launch_lds<gemm_bf16_ph_kernel<EPI>>(pg, 512, 2 * (256 + 256) * 128, st, g);
+    if (cfg == CFG_T4) {
+        constexpr int smem = TAIL_LDS_BYTES > 2 * 65536 ? TAIL_LDS_BYTES : 2 * 65536;   // two K-tile buffers; the tail's parking buffers alias them
+        constexpr int smem_x = 2 * 65536 + 4 * XPARK_BYTES;   // cross-tile form: the ring + one 8 KB parking stripe per wave above it = all 160 KB of the CU's LDS
         // one workgroup per tile: asked for by this call (otter_epilogue_args::grid_mode = 2), by the process default
         // (otter_gemm_set_persistent(0)) when the call leaves it open, or by debug bit 13
         const bool per_tile = g.grid_mode == OTTER_GRID_PER_TILE || (g.grid_mode == OTTER_GRID_DEFAULT && !g_persistent);
-        if ((g_order & 0x10) || per_tile) pg = grid.x;
-#define LAUNCH_T4(SCH_)                                                                                                    \
-    do {                                                                                                                   \
-        static bool once = false;                                                                                          \
-        if (!once) { int rc = set_smem(gemm_bf16_t4_kernel<EPI, SCH_>, smem); if (rc) return rc; once = true; }            \
-        hipLaunchKernelGGL((gemm_bf16_t4_kernel<EPI, SCH_>), dim3(pg), dim3(256), smem, st, g);                            \
-    } while (0)
-#define LAUNCH_T4T(TA_, TB_)                                                                                               \
-    do {                                                                                                                   \
-        static bool once = false;                                                                                          \
-        if (!once) { int rc = set_smem(gemm_bf16_t4_kernel<EPI, 0, TA_, TB_>, smem); if (rc) return rc; once = true; }     \
-        hipLaunchKernelGGL((gemm_bf16_t4_kernel<EPI, 0, TA_, TB_>), dim3(pg), dim3(256), smem, st, g);                     \
-    } while (0)
-// cross-tile form: the ring (2 x 64 KB) + one 8 KB parking stripe per wave above it = all 160 KB of the CU's LDS
-#define LAUNCH_T4X(TA_, TB_)                                                                                               \
-    do {                                                                                                                   \
-        static bool once = false;                                                                                          \
-        constexpr int smem_x = 2 * 65536 + 4 * XPARK_BYTES;                                                                \
-        if (!once) { int rc = set_smem(gemm_bf16_t4_kernel<EPI, 0, TA_, TB_, true>, smem_x); if (rc) return rc; once = true; } \
-        hipLaunchKernelGGL((gemm_bf16_t4_kernel<EPI, 0, TA_, TB_, true>), dim3(pg), dim3(256), smem_x, st, g);             \
-    } while (0)
+        const unsigned pt = ((g_order & 0x10) || per_tile) ? grid.x : pg;
         // (the cross-tile form peels two K-tiles at each end of a tile's K loop: >= 4 K-tiles)
         // K-contiguous operands only: with a K-major operand the cross-tile form measured SLOWER (dW2 404 vs 396 us, profiles/r06_xt_ab*.txt):
         // its tail is shorter, but the stores it leaves in flight hold back the in-order vmcnt waits of the next tile's first K-tiles by more
-        if (cfg == CFG_T4 && t4_xt_on() && !g.ta && !g.tb && g.K >= 256) {
-            LAUNCH_T4X(false, false);
-            return OTTER_OK;
-        }
-#undef LAUNCH_T4X
-        if (g.ta || g.tb) {   // K-major operands: the backward products (dW = dy^T x: both; dx = dy W: B)
-            if (g.ta && g.tb) LAUNCH_T4T(true, true);
-            else if (g.tb) LAUNCH_T4T(false, true);
-            else LAUNCH_T4T(true, false);
-            return OTTER_OK;
-        }
-#undef LAUNCH_T4T
-#ifdef OTTER_EXPERIMENTAL
-        if (cfg == CFG_T4) LAUNCH_T4(0);
-        else if (cfg == CFG_T4B) LAUNCH_T4(1);
-        else if (cfg == CFG_T4C) LAUNCH_T4(2);
-        else LAUNCH_T4(3);
-#else
-        LAUNCH_T4(0);
-#endif
-#undef LAUNCH_T4
-        return OTTER_OK;
+        if (t4_xt_on() && !g.ta && !g.tb && g.K >= 256) return launch_lds<gemm_bf16_t4_kernel<EPI, false, false, true>>(pt, 256, smem_x, st, g);
+        // K-major operands: the backward products (dW = dy^T x: both; dx = dy W: B)
+        if (g.ta && g.tb) return launch_lds<gemm_bf16_t4_kernel<EPI, true, true>>(pt, 256, smem, st, g);
+        if (g.tb) return launch_lds<gemm_bf16_t4_kernel<EPI, false, true>>(pt, 256, smem, st, g);
+        if (g.ta) return launch_lds<gemm_bf16_t4_kernel<EPI, true, false>>(pt, 256, smem, st, g);
+        return launch_lds<gemm_bf16_t4_kernel<EPI>>(pt, 256, smem, st, g);
     }
-    if (cfg == CFG_S4H) {
-        static bool once = false;
-        const int smem = 4 * 24576;  // the ring; the tail's parking buffers (4 waves x 1 stripe) alias it
-        if (!once) { int rc = set_smem(gemm_bf16_s4h_kernel<EPI>, smem); if (rc) return rc; once = true; }
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
-        hipLaunchKernelGGL((gemm_bf16_s4h_kernel<EPI>), dim3(pg), dim3(256), smem, st, g);
-        return OTTER_OK;
-    }
-    if (cfg == CFG_S4) {
-        static bool once = false;
-        const int smem = 4 * 32768;  // the ring; the tail's parking buffers (4 waves x 2 stripes = 69632 B) alias it
-        if (!once) { int rc = set_smem(gemm_bf16_s4_kernel<EPI>, smem); if (rc) return rc; once = true; }
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
-        hipLaunchKernelGGL((gemm_bf16_s4_kernel<EPI>), dim3(pg), dim3(256), smem, st, g);
-        return OTTER_OK;
-    }
-#ifdef OTTER_EXPERIMENTAL
-    if (cfg == CFG_Q4) {
-        static bool once = false;
-        const int smem = TAIL_LDS_BYTES;  // 4 x 32 KB ring; the tail's parking buffers (139264 B) alias it
-        if (!once) { int rc = set_smem(gemm_bf16_q4_kernel<EPI>, smem); if (rc) return rc; once = true; }
-        unsigned pg = grid.x < persistent_cus() ? grid.x : persistent_cus();
-        hipLaunchKernelGGL((gemm_bf16_q4_kernel<EPI>), dim3(pg), dim3(256), smem, st, g);
-        return OTTER_OK;
-    }
-#endif
-    return launch_one<256, 256, 2, 4, true, EPI>(grid, st, g);
+    if (cfg == CFG_S4H) return launch_lds<gemm_bf16_s4h_kernel<EPI>>(pg, 256, 4 * 24576, st, g);   // the ring; the tail's parking buffers (4 waves x 1 stripe) alias it
+    if (cfg == CFG_S4) return launch_lds<gemm_bf16_s4_kernel<EPI>>(pg, 256, 4 * 32768, st, g);     // the ring; the tail's parking buffers (4 waves x 2 stripes = 69632 B) alias it
+    return launch_tiled<256, 256, 2, 4, true, EPI>(grid.x, st, g);   // CFG_256_GLDS
 }
 
 int launch_cfg(int cfg, int kind, dim3 grid, hipStream_t st, const GemmArgs& g) {
@@ -2938,19 +2466,6 @@ int launch_cfg(int cfg, int kind, dim3 grid, hipStream_t st, const GemmArgs& g) 
 
 extern "C" {
 
-int otter_abi_version(void) { return OTTER_ABI_VERSION; }
-const char* otter_last_error(void) { return g_otter_err; }
-
-int otter_device_check(void) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess)
-        OTTER_FAIL(OTTER_ERR_LAUNCH, "no HIP device");
-    if (strncmp(p.gcnArchName, "gfx950", 6) != 0)
-        OTTER_FAIL(OTTER_ERR_UNSUPPORTED, "device is %s, this library is built for gfx950 only", p.gcnArchName);
-    return p.multiProcessorCount;
-}
-
 int otter_gemm_set_cu_budget(int cus) {
     if (cus < 0) OTTER_FAIL(OTTER_ERR_ARG, "gemm cu budget %d", cus);
     g_cu_budget = (cus > 0 && cus < 8) ? 8 : cus;   // at least one workgroup per XCD
@@ -2963,20 +2478,15 @@ int otter_gemm_set_persistent(int on) {
 }
 
 int otter_gemm_variant_available(int variant) {
-    if (variant < 0 || variant > 30 || variant == 24) return 0;
-#ifdef OTTER_EXPERIMENTAL
-    return 1;
-#else
-    // product build: auto (0), the generic 128^2 / 256^2 kernels (1-3), the phased fallback for K % 128 != 0 (13), the small-grid ring
-    // (25) and the default (26); every other schedule is compiled into the tools-only experimental library
-    return variant <= 3 || variant == CFG_PHLB || variant == CFG_S4 || variant == CFG_T4 || variant == CFG_S4H;
-#endif
+    // auto (0), the generic 128^2 / 256^2 kernels (1-3), the phased fallback for K % 128 != 0 (13), the small-grid ring (25) and its
+    // half-height form (30), and the default (26); every other number belonged to a retired schedule
+    return variant >= 0 && (variant <= 3 || variant == CFG_PHLB || variant == CFG_S4 || variant == CFG_T4 || variant == CFG_S4H);
 }
 
 int otter_gemm_set_variant(int variant) {
     if (variant < 0 || variant > 30) OTTER_FAIL(OTTER_ERR_ARG, "gemm variant %d", variant);
     if (!otter_gemm_variant_available(variant))
-        OTTER_FAIL(OTTER_ERR_UNSUPPORTED, "gemm variant %d is in the experimental build only (python -m otter_amd.build --experimental)", variant);
+        OTTER_FAIL(OTTER_ERR_UNSUPPORTED, "gemm variant %d was retired or never assigned: this library has 0-3, 13, 25, 26 and 30 (DESIGN_HISTORY.md)", variant);
     g_variant = variant;
     return OTTER_OK;
 }
@@ -2989,7 +2499,7 @@ int otter_gemm_read_timeline(unsigned long long* out, int n) {
 }
 
 int otter_gemm_set_debug(int flags) {
-    g_debug = flags & 255;  // bit 64: tile-phase timeline of variants 18-20 (otter_gemm_read_timeline)
+    g_debug = flags & 255;  // bit 64: tile-phase timeline of variant 26 (otter_gemm_read_timeline)
     g_narrow_epilogue = (flags & 256) ? 1 : 0;
     g_order = (flags >> 9) & 31;  // tile-order override (bits 9-12, see tile_of_block); bit 13: non-persistent launch of variant 26
     g_xt_force = (flags >> 14) & 3;                       // cross-tile form of variant 26: 0 default, 1 off, 2 on

@@ -653,8 +653,8 @@ def set_gemm_variant(v: int):
 
 
 def gemm_variant_available(v: int) -> bool:
-    """True when schedule `v` is compiled into the loaded library (the product build carries 0-3, 13, 25, 26; the rest live in the
-    tools-only experimental build: OTTER_LIB_PATH=otter_amd/lib/libotter_hip_experimental.so)."""
+    """True when schedule `v` is compiled into the loaded library: 0-3, 13, 25, 26, 30.  The numbers of the earlier kernel
+    generations (4-12, 14-23, 27-29) are retired; set_gemm_variant refuses them."""
     return bool(K.lib().otter_gemm_variant_available(int(v)))
 
 

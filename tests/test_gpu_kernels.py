@@ -7,7 +7,6 @@ Tolerances (stated per the brief):
                 fp32 accumulation order + one bf16 rounding of the output: 1e-2 relative-to-max for bf16 outputs,
                 1e-4 for fp32 outputs of bf16-operand GEMMs.
 """
-import os
 
 import numpy as np
 import pytest
@@ -234,21 +233,15 @@ def test_llama_ops_golden(ops):
 # GEMM (all variants, all epilogues)
 # ----------------------------------------------------------------------------------------------------------------------
 
-# The product library carries the schedules pick_cfg can choose (1-3, 13, 25, 26); the kernel generations that led to them (rounds
-# 1-2) are compiled into the tools-only experimental library and are tested only when the suite is pointed at it
-# (OTTER_LIB_PATH=otter_amd/lib/libotter_hip_experimental.so python -m pytest tests/test_gpu_kernels.py -m gpu -k gemm).
+# The library carries the schedules pick_cfg can choose (1-3, 13, 25, 26, 30); the kernel generations that led to them (rounds 1-2:
+# 4-12, 14-23, 27-29) are retired and refused by otter_gemm_set_variant.
 LIVE_VARIANTS = [1, 2, 3, 13, 25, 26, 30]
-_EXPERIMENTAL = os.environ.get("OTTER_LIB_PATH", "").endswith("experimental.so")
-
-
-def variants(*cands):
-    return [v for v in cands if v in LIVE_VARIANTS or _EXPERIMENTAL]
 
 
 GEMM_SHAPES = [(48, 128, 48), (200, 136, 328), (257, 512, 64), (64, 384, 1024), (520, 264, 200), (300, 520, 256), (513, 260, 128)]
 
 
-@pytest.mark.parametrize("variant", variants(1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 25, 26, 30))
+@pytest.mark.parametrize("variant", LIVE_VARIANTS)
 @pytest.mark.parametrize("M,N,Kd", GEMM_SHAPES)
 def test_gemm_bf16_store(ops, variant, M, N, Kd):
     ops.set_gemm_variant(variant)
@@ -276,7 +269,7 @@ def test_gemm_f32_store(ops, M, N, Kd):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("variant", variants(1, 2, 4, 6, 7, 8, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 25, 26, 30))
+@pytest.mark.parametrize("variant", [1, 2, 13, 25, 26, 30])
 def test_gemm_epilogues(ops, dt, variant):
     from otter_amd._capi import EPI_GATE_BWD, EPI_GELU, EPI_SCALE_RES, EPI_STORE
 
@@ -371,7 +364,7 @@ def test_gemm_gelu_derivative_stash(ops, dt, shape):
         ops.gemm_nt(dA, dB, out_dtype=tdt, kind=EPI_GATE_BWD, aux=to_dev(np.zeros((M, N), np.float32), tdt), aux_gelu="stash", partial=part)
 
 
-@pytest.mark.parametrize("variant", variants(17, 18, 19, 20, 21, 22, 23, 25, 26, 30))
+@pytest.mark.parametrize("variant", [25, 26, 30])
 @pytest.mark.parametrize("out_dt", ["bf16", "f32"])
 def test_gemm_full_tile_fast_tail(ops, variant, out_dt):
     """The one-wave-per-SIMD kernels take an unrolled, double-buffered tail on full in-bounds tiles: every epilogue kind and
@@ -412,10 +405,10 @@ def test_gemm_full_tile_fast_tail(ops, variant, out_dt):
     try:
         # variant 26 walks a tile's K-tiles rotated by the tile's XCD since round 6 (another fp32 summation order than variant 13's): the
         # bit-for-bit comparison of the TAILS runs it with the plain K order (otter_gemm_set_debug bit 23 = take bits 16-22 as the order: 0)
-        K_.check(K_.lib().otter_gemm_set_debug(1 << 23), "gemm_set_debug")
+        K_.gemm_set_debug(1 << 23)
         mine, base = run(variant), run(13)
     finally:
-        K_.check(K_.lib().otter_gemm_set_debug(0), "gemm_set_debug")
+        K_.gemm_set_debug(0)
         ops.set_gemm_variant(0)
     for k in base:
         if k.startswith("gpart"):   # block partials are summed in a different order (4 vs 8 waves)
@@ -427,10 +420,10 @@ def test_gemm_full_tile_fast_tail(ops, variant, out_dt):
     assert relmax(host(mine["gelu_pre"]), ref) < tol
 
 
-@pytest.mark.parametrize("variant", variants(18, 21, 22, 23, 26))
+@pytest.mark.parametrize("variant", [26])
 def test_gemm_persistent_blocks_with_several_tiles(ops, variant):
     """More tiles than CUs (17 x 16 = 272 tiles of 256 x 256, K = 384 -> the tail-trip-only K loop of nk = 6): the persistent blocks
-    walk 2 tiles each for 16 of them, which is where variant 21 prefetches the next tile's first K-tile under the tail.  Bit-exact
+    walk 2 tiles each for 16 of them, which is where the cross-tile form requests the next tile's first K-tiles from inside the K loop.  Bit-exact
     against the 8-wave kernel for a plain and a residual epilogue, and against fp64."""
     from otter_amd._capi import EPI_SCALE_RES
 
@@ -443,12 +436,12 @@ def test_gemm_persistent_blocks_with_several_tiles(ops, variant):
 
     outs = {}
     try:
-        K_.check(K_.lib().otter_gemm_set_debug(1 << 23), "gemm_set_debug")   # plain K order (variant 26 rotates it by the tile's N panel: another summation order)
+        K_.gemm_set_debug(1 << 23)   # plain K order (variant 26 rotates it by the tile's N panel: another summation order)
         for v in (13, variant):
             ops.set_gemm_variant(v)
             outs[v] = (ops.gemm_nt(A, B), ops.gemm_nt(A, B, out_dtype=torch.float32, kind=EPI_SCALE_RES, R=R))
     finally:
-        K_.check(K_.lib().otter_gemm_set_debug(0), "gemm_set_debug")
+        K_.gemm_set_debug(0)
         ops.set_gemm_variant(0)
     assert torch.equal(outs[13][0], outs[variant][0]) and torch.equal(outs[13][1], outs[variant][1])
     ref = host(A[:300]).astype(np.float64) @ host(B).astype(np.float64).T
@@ -737,7 +730,7 @@ def test_gemm_big_variants_agree(ops):
     B = to_dev(r.standard_normal((N, Kd)), torch.bfloat16)
     ref = host(A).astype(np.float64) @ host(B).astype(np.float64).T
     outs = []
-    for v in variants(1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 25, 26, 30):
+    for v in LIVE_VARIANTS:
         ops.set_gemm_variant(v)
         outs.append(ops.gemm_nt(A, B, out_dtype=torch.float32))
     ops.set_gemm_variant(0)
@@ -1117,7 +1110,7 @@ def test_scatter_rows_out_of_range_index_is_never_dereferenced(ops):
 
 def test_gemm_cu_budget_and_variant_availability(ops):
     """otter_gemm_set_cu_budget: the persistent kernels run on fewer workgroups (CUs left to a concurrent RCCL kernel) with identical
-    results; the product library rejects the experimental schedules loudly."""
+    results; the library rejects the retired schedules loudly."""
     from otter_amd import _capi
 
     r = rng(91)
@@ -1136,10 +1129,9 @@ def test_gemm_cu_budget_and_variant_availability(ops):
         total = ops.set_gemm_cu_budget(0)
     assert total == _capi.lib().otter_device_check()
     assert all(ops.gemm_variant_available(v) for v in LIVE_VARIANTS) and not ops.gemm_variant_available(24)
-    if not _EXPERIMENTAL:
-        assert not ops.gemm_variant_available(18)
-        with pytest.raises(_capi.OtterHipError, match="experimental build"):
-            ops.set_gemm_variant(18)
+    assert not ops.gemm_variant_available(18)
+    with pytest.raises(_capi.OtterHipError, match="retired"):
+        ops.set_gemm_variant(18)
 
 
 def test_decode_attention_at_the_lds_limit(ops):

@@ -38,8 +38,8 @@ from otter_amd import _capi
 res = {}
 for rnd in range(3):   # interleaved: wide (16-byte) fused tail vs the 4-wide one (debug bit 256)
     for flag, tag in ((0, "wide"), (256, "narrow")):
-        _capi.lib().otter_gemm_set_debug(flag)
+        _capi.gemm_set_debug(flag)
         for k, f in cases.items():
             res.setdefault(k + ":" + tag, []).append(bench(f))
-_capi.lib().otter_gemm_set_debug(0)
+_capi.gemm_set_debug(0)
 print(json.dumps({k: round(statistics.median(v), 1) for k, v in res.items()}))

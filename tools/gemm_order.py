@@ -25,9 +25,9 @@ for (M, N, K) in [(4096, 16384, 4096), (4096, 4096, 16384), (16384, 4096, 4096)]
         res = {}
         for r in range(rounds):
             for o in orders:
-                _capi.lib().otter_gemm_set_debug(o << 9)
+                _capi.gemm_set_debug(o << 9)
                 res.setdefault(o, []).append(bench(lambda: ops.gemm_nt(A, B, out=C, out_dtype=odt)))
-            _capi.lib().otter_gemm_set_debug(0)
+            _capi.gemm_set_debug(0)
             res.setdefault("torch", []).append(bench(lambda: torch.matmul(A, B.t(), out=C)) if odt == torch.bfloat16 else 0.0)
         print(json.dumps({"shape": [M, N, K], "out": str(odt).split(".")[-1],
                           "med_us": {("%dx%d%s" % (1 << ((o & 7) - 1), 32 >> ((o & 7) - 1), "N" if o & 8 else "M") if o else "default") if o != "torch" else "torch":

@@ -28,11 +28,11 @@ for (M, N) in [(4096, 16384), (16384, 4096), (4096, 4096)]:
                 if dbg is None:
                     fn = lambda: torch.matmul(A, B.t(), out=C)
                 else:
-                    lib.otter_gemm_set_debug(dbg)
+                    _capi.gemm_set_debug(dbg)
                     fn = lambda: ops.gemm_nt(A, B, out=C)
                 bench(fn)
                 res.setdefault(name, []).append(bench(fn))
-            lib.otter_gemm_set_debug(0)
+            _capi.gemm_set_debug(0)
         for k, v in res.items():
             fits.setdefault(k, []).append((K, statistics.median(v)))
     for k, pts in fits.items():

@@ -35,7 +35,7 @@ for rnd in range(4):
         if c is None:
             res[k].append(bench(lambda: torch.matmul(A, B.t(), out=C)))
         else:
-            _capi.lib().otter_gemm_set_debug(c[0])
+            _capi.gemm_set_debug(c[0])
             res[k].append(bench(lambda: ops.gemm_nt(c[1], c[2], out=c[3])))
-_capi.lib().otter_gemm_set_debug(0)
+_capi.gemm_set_debug(0)
 print(json.dumps({k: [round(min(v), 1), round(statistics.median(v), 1)] for k, v in res.items()}))

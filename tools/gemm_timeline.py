@@ -37,10 +37,10 @@ def launch():
 for _ in range(3):
     launch()
 torch.cuda.synchronize()
-K.lib().otter_gemm_set_debug(64)
+K.gemm_set_debug(64)
 launch()
 torch.cuda.synchronize()
-K.lib().otter_gemm_set_debug(0)
+K.gemm_set_debug(0)
 buf = np.zeros(512, dtype=np.uint64)
 K.check(K.lib().otter_gemm_read_timeline(buf.ctypes.data_as(ctypes.c_void_p), 512), "timeline")
 t = buf.reshape(2, 4, 8, 8).astype(np.int64)

@@ -41,13 +41,13 @@ def launch(i):
 
 
 def timeline(i):
-    K.lib().otter_gemm_set_debug(64)
+    K.gemm_set_debug(64)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
     launch(i)
     e.record()
     torch.cuda.synchronize()
-    K.lib().otter_gemm_set_debug(0)
+    K.gemm_set_debug(0)
     buf = np.zeros(512, dtype=np.uint64)
     K.check(K.lib().otter_gemm_read_timeline(buf.ctypes.data_as(ctypes.c_void_p), 512), "timeline")
     return buf.reshape(2, 4, 8, 8).astype(np.int64), s.elapsed_time(e) * 1e3

@@ -39,7 +39,7 @@ part = torch.empty(ops.gemm_num_partials(M, FF, bf), device="cuda")
 
 def set_mode(xt, korder=0):
     # otter_gemm_set_debug: bits 14-15 = 1 off / 2 on; bit 23 + bits 16-22 = K order / start phase override
-    K.check(K.lib().otter_gemm_set_debug(((2 if xt else 1) << 14) | (1 << 23) | ((korder & 127) << 16)), "set_debug")
+    K.gemm_set_debug(((2 if xt else 1) << 14) | (1 << 23) | ((korder & 127) << 16))
 
 
 legs = {
@@ -109,7 +109,7 @@ for rep in range(reps):
         for name, xt, ko in modes:
             set_mode(xt, ko)
             res.setdefault((k, name), []).append(timeit(fn))
-K.check(K.lib().otter_gemm_set_debug(0), "set_debug")
+K.gemm_set_debug(0)
 print("cold operands (%d sets in rotation), us per launch: min / median of %d rounds" % (NSET, reps))
 for k in legs:
     row = []

@@ -15,7 +15,7 @@ torch.manual_seed(0)
 
 
 def mode(xt):
-    K.check(K.lib().otter_gemm_set_debug(((2 if xt else 1) << 14)), "set_debug")
+    K.gemm_set_debug(((2 if xt else 1) << 14))
 
 
 shapes = [(4096, 16384, 4096), (4096, 4096, 16384), (4352, 4096, 384), (4096, 4096, 512), (4100, 12288, 256), (8192, 8192, 1024), (3900, 16384, 768)]
@@ -57,6 +57,6 @@ for (M, N, Kd) in shapes:
     ops.set_gemm_cu_budget(0)
     torch.cuda.synchronize()
     print("shape %s done" % ((M, N, Kd),), flush=True)
-K.check(K.lib().otter_gemm_set_debug(0), "set_debug")
+K.gemm_set_debug(0)
 print("gemm_xt_stress: %d launches compared bit for bit with the plain form, %d mismatches" % (total, bad))
 sys.exit(1 if bad else 0)

@@ -1,6 +1,6 @@
-"""Generates the 128-slot K-tile schedule macro of gemm_bf16_t4_kernel (csrc/gemm.hip, variant 26): variant 18's pipeline
+"""Generates the 128-slot K-tile schedule macros of gemm_bf16_t4_kernel (csrc/gemm.hip, variant 26): variant 18's pipeline
 (two 64 KB buffers, register-resident K-tile, DMA of K-tile t+2 into the buffer just freed) issued as v_mfma_f32_16x16x32_bf16.
-`python tools/gen/gemm_t4_schedule.py` prints it; paste between the GENERATED markers.
+`python tools/gen/gemm_t4_schedule.py inc > otter_amd/csrc/gemm_t4_ktile.inc` writes the file the kernel includes.
 
 One K-tile (BK = 64) of a 128x128 wave tile = 2 k-steps x 64 MFMAs (16x16x32, 16 cycles each).  Slot j = MFMA j + at most one filler.
   T0: reads of k-step 1 on even slots 0..30 (k-step 0 was read by the previous iteration), lgkmcnt(0) + barrier #1 after slot 38 (the
@@ -66,12 +66,6 @@ def schedule(name, reads, b1, dma, b2, xreads, merged=False, hooks=None, zero_fi
 
 
 T0 = schedule("KTILE_T0", {2 * r: [r] for r in range(16)}, 38, {40 + 4 * p: [p] for p in range(16)}, 94, {97 + 2 * r: [r] for r in range(16)})
-# T1: k-step-1 reads on EVERY slot 0..15, everything 8 slots earlier
-T1 = schedule("KTILE_T1", {r: [r] for r in range(16)}, 30, {32 + 4 * p: [p] for p in range(16)}, 90, {91 + 2 * r: [r] for r in range(16)})
-# T2: barrier #1 8 slots later (reads get 16 slots to land), X' reads on every slot 108..123
-T2 = schedule("KTILE_T2", {2 * r: [r] for r in range(16)}, 46, {48 + 4 * p: [p] for p in range(16)}, 106, {108 + r: [r] for r in range(16)})
-# T3: one barrier per K-tile (as KTILE_S3 of variant 22), X' reads on odd slots right after it
-T3 = schedule("KTILE_T3", {2 * r: [r] for r in range(16)}, 38, {40 + 4 * p: [p] for p in range(16)}, None, {41 + 2 * r: [r] for r in range(16)}, merged=True)
 
 
 def rd2(half, ks, r, buf):
@@ -167,6 +161,3 @@ if len(sys.argv) > 1 and sys.argv[1] == "inc":
         print(schedule_split("KTILE_X0_%d" % sh, 38, dma_x(sh), 94))
     sys.exit(0)
 print(T0)
-print(T1)
-print(T2)
-print(T3)
