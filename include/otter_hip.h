@@ -366,6 +366,24 @@ int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const flo
                                 float eps, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Int8 weight-only products of the frozen decoder during generation (the reference's serving worker offers load_in_8bit for the
+ * same model: pipeline/serve/model_worker.py:92-94).  Format: qweight int8 [N, K] row-major with row stride ldw, scale fp32 [N]:
+ * scale[n] = max_k |W[n,k]| / 127 (1 for an all-zero row), q[n,k] = clamp(round_half_even(W[n,k] / scale[n]), -127, 127).
+ *   otter_gemv_w8   y[M, N] = (x[M, K] . q[N, K]^T) * scale[N] (+ bias[N]) (then the exact-erf GELU when act == 1), 1 <= M <= 16:
+ *       the linears of a cached decode step.  x bf16 (row stride ldx), y bf16 or fp32 (row stride ldy; only the M x N block is
+ *       written), bias bf16 / fp32 or NULL.  x is not quantised; q is converted to bf16 (exact) and accumulated in fp32, the scale
+ *       multiplies the finished fp32 sum, then bias, then activation.  N >= 1, K % 16 == 0, ldw % 16 == 0, ldx % 8 == 0; x, qweight,
+ *       y 16-byte aligned.  workspace: at least OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K) bytes (fp32 split-K partials, combined in
+ *       a fixed order: two calls on the same inputs give the same bits).
+ *   otter_dequant_w8   out[n, k] = bf16(float(q[n, k]) * scale[n]), out bf16 [N, K] with row stride ldo (ldo % 8 == 0, 16-byte
+ *       aligned): the pass in front of the library GEMM when more than 16 rows arrive (prompt prefill).
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K) ((int64_t)8 * (int64_t)(M) * (int64_t)(N) * 4)   /* at most 8 K ranges, whatever K */
+int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype, void* y,
+                  int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes, void* stream);
+int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * OtterHD / Fuyu-8B path (config C5): row-wise kernels of the Persimmon decoder and the patch scatter.
  *   otter_qk_norm_rope_fwd  /root/reference/src/otter_ai/models/fuyu/modeling_persimmon.py:262-304: the per-head interleaved
  *       projection output qkv [tokens, H, 3, 64] (bf16) is read in place; q and k get LayerNorm over the 64-wide head

@@ -1,0 +1,249 @@
+// w8.hip -- int8 weight-only products of the frozen decoder during generation.
+//
+// Format (otter_amd/quant.py): qweight int8 [N, K] row-major, scale fp32 [N] (one per output row), |q| <= 127.
+//
+// otter_gemv_w8   y[M, N] = (x[M, K] . q[N, K]^T) * scale[N] (+ bias[N]) (then exact-erf GELU), 1 <= M <= 16: one cached decode step sends
+//                 B x num_beams rows through every decoder linear, so the product is a single pass over the weight.  x is NOT quantised
+//                 and the i8 matrix instruction is not used: q is converted to bf16 in registers (exact for |q| <= 127) and fed to
+//                 v_mfma_f32_16x16x32_bf16 with x padded to 16 rows; fp32 accumulation, the scale applied to the fp32 sum.
+// otter_dequant_w8  out[n, k] = bf16(float(q[n, k]) * scale[n]): the streaming pass behind the more-than-16-row (prefill) path.
+//
+// GEMV decomposition.  A workgroup of 4 waves owns 16 R output rows (R = 1, or 2 from N = 16384 up) and one of S contiguous K ranges; its
+// waves cut that range in four (split-K inside the workgroup, combined through LDS in wave order).  Per 64-wide K step a lane loads 16
+// consecutive int8 of ONE weight row (row = lane & 15, K offset 16 (lane >> 4)) straight into VGPRs -- the weight is streamed once and
+// shared with nobody, so it never touches LDS -- and the two 8-element halves are the A fragments of two MFMAs; the matching 2 x 8
+// bf16 of x row (lane & 15) are the B fragments (x is at most 512 KB and stays in L2; lanes of rows >= M load nothing).  Both operands
+// see the same permutation of K inside a step, which a dot product does not notice.  Steps are issued four at a time, the next four
+// requested before the current four are consumed.  With S > 1 (few rows, long K: out_proj, down_proj) every workgroup writes its raw
+// fp32 sums to the workspace and a second kernel adds the S ranges in order: no floating-point atomics, bit-identical from call to call.
+#include "common.h"
+
+typedef __bf16 w8_bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float w8_f32x4_t __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int NT = 256, WAVES = 4, KSTEP = 64, UNROLL = 4;
+constexpr int MAX_SPLIT = 8;              // OTTER_GEMV_W8_WORKSPACE_BYTES of the header is sized for it
+constexpr int64_t WG_TARGET = 512;        // two workgroups (8 waves) per CU of a 256-CU part
+constexpr int64_t MIN_K_PER_WG = 1024;    // a K range is split further only while each workgroup keeps this much
+
+struct W8Args {
+    const bf16_t* x; int64_t ldx;
+    const int8_t* w; int64_t ldw;
+    const float* scale;
+    const void* bias; int bias_dtype;
+    void* y; int64_t ldy; int y_dtype;
+    float* part;                          // [S, M, N] fp32 (S > 1)
+    int M, N, K, act, S;
+    int T, q;                             // K steps in all, K steps per wave
+};
+
+// 8 int8 (two dwords) -> 8 bf16, exact
+__device__ __forceinline__ w8_bf16x8_t cvt8(uint32_t lo, uint32_t hi) {
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[i] = (float)(int)(int8_t)(lo >> (8 * i));
+        f[4 + i] = (float)(int)(int8_t)(hi >> (8 * i));
+    }
+    uint4 r;
+    r.x = pack2bf(f[0], f[1]);
+    r.y = pack2bf(f[2], f[3]);
+    r.z = pack2bf(f[4], f[5]);
+    r.w = pack2bf(f[6], f[7]);
+    return __builtin_bit_cast(w8_bf16x8_t, r);
+}
+
+__device__ __forceinline__ float w8_epilogue(float v, int64_t n, const W8Args& a) {
+    v *= a.scale[n];
+    if (a.bias) v += ld_as_f32(a.bias, n, a.bias_dtype);
+    return a.act ? gelu_erf(v) : v;
+}
+
+template <int R>
+struct Batch {
+    uint4 w[UNROLL][R], xa[UNROLL], xb[UNROLL];
+};
+
+template <int R>
+__global__ __launch_bounds__(NT) void gemv_w8_kernel(W8Args a) {
+    __shared__ float red[WAVES][R][4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    const int64_t n0 = (int64_t)blockIdx.x * (16 * R);
+    const int s = blockIdx.y;
+    const int t0 = (s * WAVES + wv) * a.q, t1 = min(t0 + a.q, a.T);
+
+    const int8_t* wp[R];
+    bool row_ok[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t n = n0 + 16 * r + r16;
+        row_ok[r] = n < a.N;
+        wp[r] = a.w + (row_ok[r] ? n : 0) * a.ldw + 16 * g;
+    }
+    const bool x_ok = r16 < a.M;
+    const bf16_t* xp = a.x + (int64_t)(x_ok ? r16 : 0) * a.ldx + 16 * g;
+
+    auto load = [&](Batch<R>& b, int t) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int64_t k = (int64_t)(t + u) * KSTEP;
+            const bool ok = (t + u) < t1 && k + 16 * g < a.K;      // K % 16 == 0: a lane's 16 elements are all inside or all outside
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                b.w[u][r] = (ok && row_ok[r]) ? *reinterpret_cast<const uint4*>(wp[r] + k) : make_uint4(0, 0, 0, 0);
+            if (ok && x_ok) {
+                b.xa[u] = *reinterpret_cast<const uint4*>(xp + k);
+                b.xb[u] = *reinterpret_cast<const uint4*>(xp + k + 8);
+            } else {
+                b.xa[u] = make_uint4(0, 0, 0, 0);
+                b.xb[u] = make_uint4(0, 0, 0, 0);
+            }
+        }
+    };
+
+    // the weight rows are the MFMA's A operand and the x rows its B operand, so a tile is [weight row, x row]: y transposed (read back below)
+    w8_f32x4_t acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = w8_f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    auto consume = [&](const Batch<R>& b) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const w8_bf16x8_t xa = __builtin_bit_cast(w8_bf16x8_t, b.xa[u]), xb = __builtin_bit_cast(w8_bf16x8_t, b.xb[u]);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(b.w[u][r].x, b.w[u][r].y), xa, acc[r], 0, 0, 0);
+                acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(b.w[u][r].z, b.w[u][r].w), xb, acc[r], 0, 0, 0);
+            }
+        }
+    };
+
+    Batch<R> cur, nxt;
+    if (t0 < t1) load(cur, t0);
+    for (int t = t0; t < t1; t += 2 * UNROLL) {                     // ping-pong between the two register batches (all conditions wave-uniform)
+        const bool more = t + UNROLL < t1;
+        if (more) load(nxt, t + UNROLL);
+        consume(cur);
+        if (more) {
+            if (t + 2 * UNROLL < t1) load(cur, t + 2 * UNROLL);
+            consume(nxt);
+        }
+    }
+
+    // the four waves' partial tiles, added in wave order.  acc[r][i] of a lane = row 16 r + 4 (lane >> 4) + i, column (x row) lane & 15
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[wv][r][i][lane] = acc[r][i];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int nn = tid & 15, m = tid >> 4;                      // neighbouring threads write neighbouring columns of y
+        const int ln = (nn >> 2) * 16 + m, i = nn & 3;
+        const int64_t n = n0 + 16 * r + nn;
+        if (m >= a.M || n >= a.N) continue;
+        float v = red[0][r][i][ln];
+#pragma unroll
+        for (int w2 = 1; w2 < WAVES; ++w2) v += red[w2][r][i][ln];
+        if (a.S == 1) st_from_f32(a.y, (int64_t)m * a.ldy + n, a.y_dtype, w8_epilogue(v, n, a));
+        else a.part[((int64_t)s * a.M + m) * a.N + n] = v;
+    }
+}
+
+// S > 1: one thread per output element adds the S ranges in order
+__global__ __launch_bounds__(NT) void gemv_w8_reduce_kernel(W8Args a) {
+    const int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (e >= (int64_t)a.M * a.N) return;
+    const int64_t m = e / a.N, n = e % a.N;
+    float v = a.part[e];
+    for (int s = 1; s < a.S; ++s) v += a.part[(int64_t)s * a.M * a.N + e];
+    st_from_f32(a.y, m * a.ldy + n, a.y_dtype, w8_epilogue(v, n, a));
+}
+
+// one workgroup per weight row, 16 elements per thread and trip
+__global__ __launch_bounds__(NT) void dequant_w8_kernel(const int8_t* __restrict__ q, int64_t ldw, const float* __restrict__ scale,
+                                                        bf16_t* __restrict__ out, int64_t ldo, int K) {
+    const int64_t n = blockIdx.x;
+    const float sc = scale[n];
+    const int8_t* qr = q + n * ldw;
+    bf16_t* orow = out + n * ldo;
+    for (int k = 16 * threadIdx.x; k < K; k += 16 * NT) {
+        const uint4 v = *reinterpret_cast<const uint4*>(qr + k);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        uint4 o[2];
+        uint32_t* op = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float f[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) f[i] = (float)(int)(int8_t)(w[j] >> (8 * i)) * sc;
+            op[2 * j] = pack2bf(f[0], f[1]);
+            op[2 * j + 1] = pack2bf(f[2], f[3]);
+        }
+        *reinterpret_cast<uint4*>(orow + k) = o[0];
+        *reinterpret_cast<uint4*>(orow + k + 8) = o[1];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype, void* y,
+                  int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes, void* stream) {
+    OTTER_REQUIRE(x && qweight && scale && y && workspace, "gemv_w8: null pointer");
+    OTTER_REQUIRE(M >= 1 && M <= 16, "gemv_w8: M=%d outside [1, 16]", (int)M);
+    OTTER_REQUIRE(N >= 1 && N <= (int64_t)1 << 30, "gemv_w8: N=%ld outside [1, 2^30]", (long)N);
+    OTTER_REQUIRE(K >= 16 && K % 16 == 0 && K <= (int64_t)1 << 30, "gemv_w8: K=%d must be a positive multiple of 16", (int)K);
+    OTTER_REQUIRE(ldw % 16 == 0 && ldx % 8 == 0 && (((uintptr_t)x | (uintptr_t)qweight | (uintptr_t)y) & 15) == 0,
+                  "gemv_w8: alignment (x, qweight, y 16-byte aligned; ldw %% 16 == 0; ldx %% 8 == 0)");
+    OTTER_REQUIRE(ldw >= K && ldx >= K && ldy >= N, "gemv_w8: a leading dimension is smaller than the row it holds");
+    OTTER_REQUIRE((y_dtype == OTTER_F32 || y_dtype == OTTER_BF16) && (!bias || bias_dtype == OTTER_F32 || bias_dtype == OTTER_BF16),
+                  "gemv_w8: y / bias dtype must be OTTER_F32 or OTTER_BF16");
+    OTTER_REQUIRE(act == 0 || act == 1, "gemv_w8: act=%d (0 none, 1 GELU)", act);
+    const int64_t need = OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K);
+    OTTER_REQUIRE(workspace_bytes >= need, "gemv_w8: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+
+    const int R = N >= 16384 ? 2 : 1;
+    const int64_t base = cdiv64(N, 16 * R);
+    int S = 1;
+    while (base * S < WG_TARGET && S < MAX_SPLIT && K / (2 * S) >= MIN_K_PER_WG) S *= 2;
+    OTTER_REQUIRE(S <= 65535, "gemv_w8: internal split");
+
+    W8Args a;
+    a.x = (const bf16_t*)x; a.ldx = ldx;
+    a.w = (const int8_t*)qweight; a.ldw = ldw;
+    a.scale = scale; a.bias = bias; a.bias_dtype = bias_dtype;
+    a.y = y; a.ldy = ldy; a.y_dtype = y_dtype;
+    a.part = (float*)workspace;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.act = act; a.S = S;
+    a.T = (int)cdiv64(K, KSTEP);
+    a.q = (int)cdiv64(a.T, (int64_t)S * WAVES);
+    hipStream_t st = (hipStream_t)stream;
+    if (R == 2) hipLaunchKernelGGL(gemv_w8_kernel<2>, dim3((unsigned)base, (unsigned)S), dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL(gemv_w8_kernel<1>, dim3((unsigned)base, (unsigned)S), dim3(NT), 0, st, a);
+    OTTER_CHECK_LAUNCH("gemv_w8");
+    if (S > 1) {
+        hipLaunchKernelGGL(gemv_w8_reduce_kernel, dim3((unsigned)cdiv64(M * N, NT)), dim3(NT), 0, st, a);
+        OTTER_CHECK_LAUNCH("gemv_w8 (reduce)");
+    }
+    return OTTER_OK;
+}
+
+int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream) {
+    OTTER_REQUIRE(qweight && scale && out, "dequant_w8: null pointer");
+    OTTER_REQUIRE(N >= 1 && N <= (int64_t)1 << 30, "dequant_w8: N=%ld outside [1, 2^30]", (long)N);
+    OTTER_REQUIRE(K >= 16 && K % 16 == 0 && K <= (int64_t)1 << 30, "dequant_w8: K=%d must be a positive multiple of 16", (int)K);
+    OTTER_REQUIRE(ldw % 16 == 0 && ldo % 8 == 0 && (((uintptr_t)qweight | (uintptr_t)out) & 15) == 0,
+                  "dequant_w8: alignment (qweight, out 16-byte aligned; ldw %% 16 == 0; ldo %% 8 == 0)");
+    OTTER_REQUIRE(ldw >= K && ldo >= K, "dequant_w8: a leading dimension is smaller than the row it holds");
+    hipLaunchKernelGGL(dequant_w8_kernel, dim3((unsigned)N), dim3(NT), 0, (hipStream_t)stream, (const int8_t*)qweight, ldw, scale, (bf16_t*)out,
+                       ldo, (int)K);
+    OTTER_CHECK_LAUNCH("dequant_w8");
+    return OTTER_OK;
+}
+
+}  // extern "C"

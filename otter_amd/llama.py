@@ -30,7 +30,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from . import functional as OF
 from . import ops
-from .mpt import FrozenAwareLinear
+from .mpt import FrozenAwareLinear, _is_int8
 
 
 def _rotate_half(x):
@@ -99,7 +99,7 @@ class _FusedFrozenLinear:
         self._w = self._wt = None
 
     def usable(self, x) -> bool:
-        return (x.is_cuda and all(m.bias is None and not m.weight.requires_grad for m in self.mods)
+        return (x.is_cuda and all(isinstance(m, nn.Linear) and m.bias is None and not m.weight.requires_grad for m in self.mods)
                 and os.environ.get("OTTER_NO_FUSED_LLAMA") != "1")
 
     def __call__(self, x, cd):
@@ -128,6 +128,12 @@ class LlamaMLP(nn.Module):
 
     def forward(self, x):
         cd = OF.compute_dtype_for(x)
+        if any(_is_int8(m) for m in (self.gate_proj, self.up_proj, self.down_proj)):
+            # int8 decoder (otter_amd/quant.py): two quantised products instead of the fused gate|up weight (per-row scales: same numbers)
+            g, u = self.gate_proj(x), self.up_proj(x)
+            if g.is_cuda and g.dtype == torch.bfloat16 and u.dtype == torch.bfloat16 and g.shape[-1] % 8 == 0:
+                return self.down_proj(OF.swiglu(torch.cat((g, u), dim=-1)))
+            return self.down_proj(F.silu(g) * u)
         if cd == torch.bfloat16 and self._gu.usable(x) and self.gate_proj.out_features % 8 == 0:
             gu = self._gu(x, cd)                         # [..., 2*I] = gate | up
             return self.down_proj(OF.swiglu(gu))
@@ -155,6 +161,10 @@ class LlamaAttention(nn.Module):
     def flash_ok(self, x, s_past: int, default_positions: bool) -> bool:
         if any(hasattr(p, "lora_delta") for p in (self.q_proj, self.k_proj, self.v_proj)):
             return False      # LoRA adapters (otter_amd/lora.py) live in the modules' own forward: the fused q|k|v weight would bypass them
+        n_int8 = sum(_is_int8(p) for p in (self.q_proj, self.k_proj, self.v_proj))
+        if n_int8:            # int8 decoder (otter_amd/quant.py): three quantised products written side by side stand in for the fused weight
+            return (n_int8 == 3 and x.is_cuda and OF.compute_dtype_for(x) == torch.bfloat16 and self.head_dim == 128 and self.n_kv == self.n_heads
+                    and s_past == 0 and default_positions and os.environ.get("OTTER_NO_FLASH") != "1")
         return (x.is_cuda and OF.compute_dtype_for(x) == torch.bfloat16 and self.head_dim == 128 and self.n_kv == self.n_heads
                 and s_past == 0 and default_positions and self._qkv.usable(x) and os.environ.get("OTTER_NO_FLASH") != "1")
 
@@ -164,7 +174,10 @@ class LlamaAttention(nn.Module):
         B, S, _ = x.shape
         H, Hk, d = self.n_heads, self.n_kv, self.head_dim
         if flash:
-            qkv = self._qkv(x, torch.bfloat16)                                  # [B,S,3*H*d]
+            if _is_int8(self.q_proj):
+                qkv = torch.cat((self.q_proj(x), self.k_proj(x), self.v_proj(x)), dim=-1)
+            else:
+                qkv = self._qkv(x, torch.bfloat16)                              # [B,S,3*H*d]
             ctx, k_rot, v = OF.rope_flash_attention(qkv, cos, sin, key_valid, H, self.scale, want_kv=use_cache)
             new_past = (k_rot.transpose(1, 2), v.transpose(1, 2)) if use_cache else None   # [B,H,S,d] like HF's legacy cache
             return self.o_proj(ctx), new_past

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import os
 import random
+import sys
 import warnings
 from typing import List, Optional
 
@@ -455,6 +456,26 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         # drops the requires_grad flags set by init_weights() in __init__ (the pinned 4.35.1 loaded in place): re-apply.
         model.init_weights()
         return model
+
+    def quantize_decoder_int8(self) -> dict:
+        """Opt-in, for generation: hold the frozen decoder's linears as int8 weights with one fp32 scale per output row
+        (otter_amd/quant.py: `quantize_frozen_decoder`), put the model in eval mode and return {"replaced", "bytes_before", "bytes_after"}.
+
+        This is an IN-MEMORY transformation done after loading: checkpoints stay in the reference's format.  `state_dict()` of a quantised
+        model (qweight / scale buffers instead of weights) is not a reference-format checkpoint, so `save_pretrained` on it raises; the
+        quantised decoder is inference-only (no autograd through it).  Calling it again replaces nothing."""
+        from .quant import quantize_frozen_decoder
+
+        info = quantize_frozen_decoder(self.lang_encoder)
+        self.eval()
+        return info
+
+    def save_pretrained(self, *args, **kwargs):
+        quant = sys.modules.get(__package__ + ".quant")          # (not loaded: nothing was ever quantised)
+        if quant is not None and any(isinstance(m, quant.Int8FrozenLinear) for m in self.modules()):
+            raise RuntimeError("save_pretrained: the decoder of this model was quantised in memory (quantize_decoder_int8); its state_dict is "
+                               "not a reference-format checkpoint.  Save the model before quantising it.")
+        return super().save_pretrained(*args, **kwargs)
 
     # ---- accessors used by pipeline/train/instruction_following.py ----
     def get_input_embeddings(self) -> nn.Module:

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 import os
+import sys
 from typing import List, Optional, Tuple
 
 import torch
@@ -150,6 +151,12 @@ def _own_attn_linear(out_features: int, in_features: int) -> bool:
     return False
 
 
+def _is_int8(m) -> bool:
+    """isinstance(m, quant.Int8FrozenLinear) without importing otter_amd.quant: a model that was never quantised never loads that module."""
+    q = sys.modules.get(__package__ + ".quant")
+    return q is not None and isinstance(m, q.Int8FrozenLinear)
+
+
 def _lin(x, w):
     return F.linear(x, w)
 
@@ -230,6 +237,10 @@ class MPTMLP(nn.Module):
 
     def forward(self, x):
         up, dn = self.up_proj, self.down_proj
+        if _is_int8(up) or _is_int8(dn):
+            # int8 decoder (otter_amd/quant.py): no `.weight` for the fused branches below; the GELU rides in the GEMV epilogue at <= 16 rows
+            h = up(x, act="gelu") if _is_int8(up) else OF.gelu(up(x))
+            return dn(h)
         if (_own_gemm() and x.is_cuda and up.bias is None and dn.bias is None and not up.weight.requires_grad and not dn.weight.requires_grad
                 and OF.compute_dtype_for(x) == torch.bfloat16):
             xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)

@@ -537,6 +537,62 @@ def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past,
     return o, k_new, v_new
 
 
+GEMV_W8_MAX_ROWS = 16                  # include/otter_hip.h: 1 <= M <= 16
+
+
+def gemv_w8_workspace_bytes(M: int, N: int, K: int) -> int:
+    """OTTER_GEMV_W8_WORKSPACE_BYTES of include/otter_hip.h."""
+    return 8 * M * N * 4
+
+
+def _w8_weight_ok(qweight, scale) -> bool:
+    return (qweight.dtype == torch.int8 and qweight.dim() == 2 and qweight.stride(1) == 1 and qweight.stride(0) % 16 == 0
+            and qweight.shape[1] % 16 == 0 and qweight.data_ptr() % 16 == 0 and scale.dtype == torch.float32 and scale.is_contiguous()
+            and scale.numel() == qweight.shape[0])
+
+
+def gemv_w8(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfloat16, out=None):
+    """y [M, N] = (x [M, K] . qweight [N, K]^T) * scale [N] (+ bias) (then exact-erf GELU when act == 1), 1 <= M <= 16
+    (otter_gemv_w8, csrc/w8.hip).  x bf16 with unit column stride, qweight int8 (row stride % 16 == 0), scale fp32 [N], bias bf16 / fp32 [N]
+    or None; y bf16 or fp32 (`out`: a caller-owned [M, N] view with unit column stride, written in place)."""
+    K.require_cuda(x, qweight, scale, bias, out)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise K.OtterHipError("gemv_w8: x must be bf16 [M, K] with a unit column stride")
+    if not _w8_weight_ok(qweight, scale):
+        raise K.OtterHipError("gemv_w8: qweight int8 [N, K] (K % 16 == 0, row stride % 16 == 0, 16-B aligned), scale contiguous fp32 [N]")
+    M, Kd = x.shape
+    N = qweight.shape[0]
+    if Kd != qweight.shape[1] or not 1 <= M <= GEMV_W8_MAX_ROWS:
+        raise K.OtterHipError(f"gemv_w8: x {tuple(x.shape)} against qweight {tuple(qweight.shape)} (1 <= M <= {GEMV_W8_MAX_ROWS})")
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        raise K.OtterHipError("gemv_w8: bias must be contiguous [N]")
+    y = torch.empty((M, N), dtype=out_dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.device != x.device:
+        raise K.OtterHipError("gemv_w8: out must be [M, N] with a unit column stride on x's device")
+    ldx, ldy = (x.stride(0), y.stride(0)) if M > 1 else (Kd, N)      # (the row stride of a one-row view is arbitrary)
+    ws = _ws.get(gemv_w8_workspace_bytes(M, N, Kd), x.device)
+    K.check(K.lib().otter_gemv_w8(x.data_ptr(), ldx, qweight.data_ptr(), qweight.stride(0), scale.data_ptr(), K.ptr(bias),
+                                  K.dt(bias) if bias is not None else K.F32, y.data_ptr(), ldy, K.dt(y), M, N, Kd, int(act), ws.data_ptr(),
+                                  ws.numel(), K.stream()), "gemv_w8")
+    return y
+
+
+def dequant_w8(qweight, scale, out=None):
+    """out [N, K] bf16 = bf16(float(qweight) * scale[:, None]) (otter_dequant_w8, csrc/w8.hip); `out`: a caller-owned bf16 [N, K] view with
+    unit column stride and a row stride that is a multiple of 8."""
+    K.require_cuda(qweight, scale, out)
+    if not _w8_weight_ok(qweight, scale):
+        raise K.OtterHipError("dequant_w8: qweight int8 [N, K] (K % 16 == 0, row stride % 16 == 0, 16-B aligned), scale contiguous fp32 [N]")
+    N, Kd = qweight.shape
+    if out is None:
+        out = torch.empty((N, Kd), dtype=torch.bfloat16, device=qweight.device)
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (N, Kd) or out.stride(1) != 1 or out.device != qweight.device:
+        raise K.OtterHipError("dequant_w8: out must be bf16 [N, K] with a unit column stride on qweight's device")
+    K.check(K.lib().otter_dequant_w8(qweight.data_ptr(), qweight.stride(0), scale.data_ptr(), out.data_ptr(), out.stride(0), N, Kd, K.stream()),
+            "dequant_w8")
+    return out
+
+
 def qk_norm_rope_fwd(qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, width=128, copy_v=True):
     """qkv [B,S,H*3*64] bf16 (per head q|k|v) -> q', k', v as [B,S,H,width] bf16, stats [B*S,H,2,2].  width 128: upper 64 columns zero
     (the 128-wide flash kernels); width 64: compact heads (the head-pair kernels), and with copy_v=False v is returned as the strided

@@ -1,0 +1,184 @@
+"""Int8 weight-only form of the frozen decoder for generation.
+
+`generate(use_cache=True)` feeds the frozen decoder one token per sequence: every decoder linear sees B x num_beams rows (1 to 16) and
+the step is a single pass over the weights.  Storing those weights as int8 with one fp32 scale per output row halves the bytes a step
+moves and the decoder's footprint; the activations stay bf16 and the accumulation fp32 (csrc/w8.hip).  This is an opt-in, in-memory
+transformation applied after loading (`OtterForConditionalGeneration.quantize_decoder_int8()`); nothing on the training path changes.
+
+Format.  For a weight W [N, K] read as fp32:
+    amax[n]  = max_k |W[n, k]|
+    scale[n] = amax[n] / 127          (fp32 IEEE division; 1 when amax[n] == 0)
+    q[n, k]  = clamp(round_half_even(W[n, k] / scale[n]), -127, 127)  as int8 (-128 is never produced)
+stored as `qweight` int8 [N, K] (row-major) and `scale` fp32 [N].  The quantiser is a handful of IEEE-exact torch ops, so it gives the
+same bits on the GPU and on the CPU.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import functional as OF
+from . import ops
+
+GEMV_MAX_ROWS = ops.GEMV_W8_MAX_ROWS
+
+
+def quantize_weight_int8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """W [N, K] (bf16 / fp16 / fp32) -> (qweight int8 [N, K], scale fp32 [N]) on W's device, by the definition in the module docstring."""
+    if w.dim() != 2 or not w.is_floating_point():
+        raise ValueError("quantize_weight_int8: a 2-d floating-point weight is expected, got %s %s" % (tuple(w.shape), w.dtype))
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    # tensor / tensor: a true division on every backend (a Python-scalar divisor may be turned into a multiplication by its reciprocal)
+    scale = amax / torch.full_like(amax, 127.0)
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    q = torch.round(wf / scale[:, None]).clamp_(-127, 127).to(torch.int8)
+    return q.contiguous(), scale.contiguous()
+
+
+def dequantize_weight_int8(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(qweight, scale) -> float(q) * scale[:, None] in fp32, rounded once to `dtype`."""
+    return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+# one bf16 scratch per device for the dequantised weight of the more-than-16-row path: sized to the largest weight seen, shared by every
+# layer (work on one device is ordered by the stream the kernels are launched on, as for ops._ws)
+_scratch: Dict[Tuple[str, Optional[int]], torch.Tensor] = {}
+
+
+def _dequant_scratch(numel: int, device: torch.device) -> torch.Tensor:
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    b = _scratch.get(key)
+    if b is None or b.numel() < numel:
+        _scratch.pop(key, None)                    # (the smaller buffer is released before the larger one is allocated)
+        del b
+        b = torch.empty(numel, dtype=torch.bfloat16, device=device)
+        _scratch[key] = b
+    return b
+
+
+def release_scratch() -> None:
+    """Drop the shared dequantisation scratch buffers (reallocated by the next prefill)."""
+    _scratch.clear()
+
+
+class Int8FrozenLinear(nn.Module):
+    """A frozen nn.Linear held as int8 weights + one fp32 scale per output row (buffers `qweight`, `scale`, `bias`).  Inference only.
+
+    forward(x, act=None) -- `act="gelu"` applies the exact-erf GELU to the output:
+      * GPU input of at most 16 rows (leading dimensions flattened): `ops.gemv_w8`, one pass over the int8 weight, scale / bias / GELU in
+        its epilogue.  x is cast to bf16 if it is not; the output has the compute dtype the unquantised layer would have produced.
+      * GPU input of more than 16 rows (prompt prefill): `ops.dequant_w8` into the process-wide bf16 scratch, then the library GEMM.
+      * CPU input: F.linear(x, dequantize_weight_int8(...), bias).  The ONE deliberate exception to this package's "no CPU fallback"
+        rule: the host contract (module swap, parity with the fake-quantised model, error paths) has to be testable without a GPU.  No
+        product path runs the decoder on the CPU.
+    """
+
+    def __init__(self, qweight: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        super().__init__()
+        if qweight.dtype != torch.int8 or qweight.dim() != 2 or scale.dtype != torch.float32 or tuple(scale.shape) != (qweight.shape[0],):
+            raise ValueError("Int8FrozenLinear: qweight int8 [N, K] and scale fp32 [N] are expected")
+        self.out_features, self.in_features = qweight.shape
+        self.register_buffer("qweight", qweight.contiguous())
+        self.register_buffer("scale", scale.contiguous())
+        self.register_buffer("bias", None if bias is None else bias.detach().clone())
+
+    def _apply(self, fn, *a, **k):
+        # .half() / .to(torch.bfloat16) cast floating-point buffers: the scale is part of the format and stays fp32 (qweight is int8 and
+        # is never cast); moves between devices go through as usual
+        exact = self.scale
+        super()._apply(fn, *a, **k)
+        if self.scale.dtype != torch.float32:
+            self.scale = exact.to(self.scale.device)
+        return self
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear) -> "Int8FrozenLinear":
+        if lin.weight.requires_grad:
+            raise ValueError("Int8FrozenLinear.from_linear: the layer is trainable (weight.requires_grad); only frozen layers are quantised")
+        q, s = quantize_weight_int8(lin.weight)
+        return cls(q, s, lin.bias)
+
+    def extra_repr(self) -> str:
+        return "in_features=%d, out_features=%d, bias=%s, int8" % (self.in_features, self.out_features, self.bias is not None)
+
+    def nbytes(self) -> int:
+        return self.qweight.numel() + 4 * self.scale.numel() + (self.bias.numel() * self.bias.element_size() if self.bias is not None else 0)
+
+    def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
+        if act not in (None, "gelu"):
+            raise ValueError("Int8FrozenLinear: act must be None or 'gelu'")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("the int8 decoder is inference-only: its input requires grad (run it under torch.no_grad(); training or LoRA "
+                               "on quantised weights is not supported)")
+        if not x.is_cuda:
+            y = F.linear(x, dequantize_weight_int8(self.qweight, self.scale, x.dtype), None if self.bias is None else self.bias.to(x.dtype))
+            return F.gelu(y) if act else y
+        cd = OF.compute_dtype_for(x)
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, self.in_features)
+        xb = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
+        if xb.shape[0] <= GEMV_MAX_ROWS:
+            if xb.stride(1) != 1 or (xb.shape[0] > 1 and xb.stride(0) % 8) or xb.data_ptr() % 16:
+                xb = xb.contiguous()
+            y = ops.gemv_w8(xb, self.qweight, self.scale, self.bias, 1 if act else 0, out_dtype=cd)
+            return y.view(lead + (self.out_features,))
+        n, k = self.qweight.shape
+        w = ops.dequant_w8(self.qweight, self.scale, out=_dequant_scratch(n * k, x.device)[: n * k].view(n, k))
+        with torch.autocast("cuda", enabled=False):
+            y = F.linear(xb, w, None if self.bias is None else self.bias.to(torch.bfloat16))
+        if act:
+            y = OF.gelu(y)
+        return (y if cd == torch.bfloat16 else y.to(cd)).view(lead + (self.out_features,))
+
+
+def _decoder_layers(lang_encoder: nn.Module):
+    if hasattr(lang_encoder, "_get_decoder_layers"):
+        return list(lang_encoder._get_decoder_layers())
+    for path in ("transformer.blocks", "model.layers"):
+        obj = lang_encoder
+        try:
+            for part in path.split("."):
+                obj = getattr(obj, part)
+        except AttributeError:
+            continue
+        return list(obj)
+    raise ValueError("quantize_frozen_decoder: no decoder layers found in %s" % lang_encoder.__class__.__name__)
+
+
+def quantize_frozen_decoder(lang_encoder: nn.Module) -> dict:
+    """Replace every frozen FrozenAwareLinear inside the decoder layers (MPT: Wqkv, out_proj, up_proj, down_proj; LLaMA: q/k/v/o_proj,
+    gate/up/down_proj) by an Int8FrozenLinear.  Left alone: LoRA-wrapped layers, anything trainable, the embedding / tied un-embedding and
+    lm_head, the gated cross-attention blocks (and the perceiver and CLIP, which are not part of the language model).  The compute-dtype and
+    transposed copies of what is replaced are released.  Returns {"replaced", "bytes_before", "bytes_after"}; a second call replaces nothing."""
+    from .lora import LoraLinear
+    from .mpt import FrozenAwareLinear
+
+    replaced, before, after = 0, 0, 0
+    for layer in _decoder_layers(lang_encoder):
+        core = getattr(layer, "decoder_layer", layer)          # OtterLayer wraps (gated_cross_attn_layer, decoder_layer)
+        swapped = {}
+        for parent in list(core.modules()):
+            for name, child in list(parent.named_children()):
+                if (not isinstance(child, FrozenAwareLinear) or isinstance(child, LoraLinear) or child.weight.requires_grad
+                        or (child.bias is not None and child.bias.requires_grad) or child.in_features % 16):
+                    continue
+                new = Int8FrozenLinear.from_linear(child)
+                before += child.weight.numel() * child.weight.element_size()
+                before += child.bias.numel() * child.bias.element_size() if child.bias is not None else 0
+                after += new.nbytes()
+                child.release_copies()
+                setattr(parent, name, new)
+                swapped[id(child)] = new
+                replaced += 1
+        if swapped:
+            for parent in core.modules():                       # the LLaMA host's fused q|k|v / gate|up helpers hold their modules by reference
+                for attr in ("_qkv", "_gu"):
+                    f = getattr(parent, attr, None)
+                    if f is not None and hasattr(f, "mods"):
+                        f.release()
+                        f.mods = [swapped.get(id(m), m) for m in f.mods]     # (or the replaced weights stay alive; `usable()` is False for these)
+    return {"replaced": replaced, "bytes_before": before, "bytes_after": after}
