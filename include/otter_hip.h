@@ -366,6 +366,37 @@ int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const flo
                                 float eps, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_decode_attn_cached -- one cached decode step over a STATIC key / value cache (otter_amd/kv_cache.py), head_dim 128: the new
+ * key / value of each of the N rows (batch x beams, all at position `pos`) are written in place into slot [n, h, pos] of a
+ * preallocated cache, and the row's single query attends over keys 0..pos -- keys before `pos` read through a beam indirection table.
+ *   q / k_new / v_new  bf16, indexed [n, h, 128] through their own row and head strides (elements), unit dim stride, 16-byte aligned,
+ *            strides multiples of 8: three slices of one fused projection row (MPT) or three projection outputs (LLaMA), read in place.
+ *   cos_rows / sin_rows  fp32 rows of 128 (the rotary table at position pos, cat(freqs, freqs) layout) with a row stride in elements
+ *            (0 = one row shared by every n), or both NULL.  When given, q and k_new are rotated, x c + rotate_half(x) s with
+ *            rotate_half(x) = (-x[64:], x[:64]); the rotation is evaluated exactly enough that k is rounded to bf16 ONCE, and that
+ *            rounded k is both stored and used for this step's own score of key pos.
+ *   k_cache / v_cache  bf16, indexed [row, h, key, 128]: row and head strides in elements (multiples of 8, head stride >= S_max * 128),
+ *            key stride 128, capacity S_max keys.  Only slot [n, :, pos, :] of each row n is written.
+ *   src      int32 [N, >= pos] with a row stride, or NULL: src[n, t] = the cache row holding sequence n's key / value at position
+ *            t < pos (NULL: the row's own).  Entries outside [0, N) are clamped into it.
+ *   key_valid  uint8 [N, >= pos + 1] with a row stride (0 = padded key), or NULL.  A row with every key masked gives o = 0.
+ *   alibi_slopes  fp32 [H] or NULL: bias slope * (j - pos) on key j.
+ *   o        bf16 [N, H * 128] contiguous.
+ *   workspace  fp32 scratch of at least OTTER_DECODE_CACHED_WORKSPACE_BYTES(N, H, pos + 1) bytes (split partials).
+ * 1 <= pos < S_max <= 65536.  No workgroup reads a slot this call writes (reads: keys < pos; writes: slot pos of the own row; key pos is
+ * taken from the new token itself), which is what makes the in-place update safe.  Key ranges are combined in a fixed order: two calls
+ * on the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_DECODE_CACHED_WORKSPACE_BYTES(N, H, Sk) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(Sk) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                             int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                             const float* cos_rows, const float* sin_rows, int64_t cos_row_stride, void* k_cache, int64_t k_cache_row_stride,
+                             int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride, int64_t v_cache_head_stride,
+                             const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride,
+                             const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos,
+                             int64_t S_max, int64_t head_dim, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Int8 weight-only products of the frozen decoder during generation (the reference's serving worker offers load_in_8bit for the
  * same model: pipeline/serve/model_worker.py:92-94).  Format: qweight int8 [N, K] row-major with row stride ldw, scale fp32 [N]:
  * scale[n] = max_k |W[n,k]| / 127 (1 for an all-zero row), q[n,k] = clamp(round_half_even(W[n,k] / scale[n]), -127, 127).

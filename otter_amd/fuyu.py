@@ -458,6 +458,12 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
         from .generation import generate_tokens
 
         use_cache = bool(generate_kwargs.pop("use_cache", getattr(self.config.text_config, "use_cache", True)))
+        cache_impl = generate_kwargs.pop("cache_implementation", None)
+        if cache_impl == "static":
+            raise NotImplementedError("FuyuForCausalLM.generate: cache_implementation='static' is not built for the Persimmon host (head_dim 64, "
+                                      "fused q/k LayerNorm + partial rotary): use the default cache, whose step runs on csrc/persimmon_decode.hip")
+        if cache_impl not in (None, "dynamic"):
+            raise ValueError("generate: cache_implementation must be None, 'dynamic' or 'static', got %r" % (cache_impl,))
         L0 = input_ids.shape[1]
         nb = int(generate_kwargs.get("num_beams", 1) or 1)
         patches, idx0 = image_patches, image_patches_indices

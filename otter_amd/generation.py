@@ -152,6 +152,15 @@ class _BeamHyps:
 StepFn = Callable[[torch.Tensor, Optional[torch.Tensor], object, Optional[torch.Tensor]], Tuple[torch.Tensor, object]]
 
 
+def resolve_max_length(prompt_len: int, max_new_tokens: Optional[int] = None, max_length: Optional[int] = None) -> int:
+    """The total length (prompt included) generation stops at: `max_new_tokens` wins over `max_length`; neither: 20 new tokens."""
+    if max_new_tokens is not None:
+        return prompt_len + int(max_new_tokens)
+    if max_length is not None:
+        return int(max_length)
+    return prompt_len + 20
+
+
 @torch.no_grad()
 def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, *, max_new_tokens: Optional[int] = None,
                     max_length: Optional[int] = None, eos_token_id=None, pad_token_id: Optional[int] = None, num_beams: int = 1,
@@ -184,12 +193,7 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
     eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
     if pad_token_id is None:
         pad_token_id = eos[0] if eos else 0
-    if max_new_tokens is not None:
-        max_len = L0 + int(max_new_tokens)
-    elif max_length is not None:
-        max_len = int(max_length)
-    else:
-        max_len = L0 + 20
+    max_len = resolve_max_length(L0, max_new_tokens, max_length)
     proc = _Processors(L0, eos, repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, min_length, prefix_allowed_tokens_fn,
                        beams_per_sentence=(num_beams // num_beam_groups if num_beam_groups > 1 else num_beams))
     if max_len <= L0:

@@ -30,6 +30,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from . import functional as OF
 from . import ops
+from .kv_cache import StaticKVCache
 from .mpt import FrozenAwareLinear, _is_int8
 
 
@@ -168,11 +169,26 @@ class LlamaAttention(nn.Module):
         return (x.is_cuda and OF.compute_dtype_for(x) == torch.bfloat16 and self.head_dim == 128 and self.n_kv == self.n_heads
                 and s_past == 0 and default_positions and self._qkv.usable(x) and os.environ.get("OTTER_NO_FLASH") != "1")
 
-    def forward(self, x, cos, sin, attn_mask=None, key_valid=None, past_key_value=None, use_cache=False, flash=False):
+    def forward(self, x, cos, sin, attn_mask=None, key_valid=None, past_key_value=None, use_cache=False, flash=False, static=None):
         """x [B,S,D] (compute dtype); cos/sin fp32 [S, d] for this call's positions (or [B,S,d] with custom position_ids);
         attn_mask: additive [B or 1,1,S,Sk] for the plain path; key_valid uint8 [B,S] for the flash path."""
         B, S, _ = x.shape
         H, Hk, d = self.n_heads, self.n_kv, self.head_dim
+        if static is not None:
+            # cached step over a StaticKVCache (otter_amd/kv_cache.py; csrc/decode_cache.hip on the GPU in bf16 at head_dim 128): the rotary
+            # embedding of the one new position, the in-place append and the attention through the beam table are one call on the
+            # projection outputs -- no torch rotary ops, no cat
+            cache, layer = static
+            n_int8 = sum(_is_int8(p) for p in (self.q_proj, self.k_proj, self.v_proj))
+            lora = any(hasattr(p, "lora_delta") for p in (self.q_proj, self.k_proj, self.v_proj))
+            if not n_int8 and not lora and OF.compute_dtype_for(x) == torch.bfloat16 and self._qkv.usable(x):
+                qkv = self._qkv(x, torch.bfloat16)[:, 0]                        # [B, (H + 2 Hk) d]: q | k | v, read in place
+                q, k, v = qkv[:, :H * d], qkv[:, H * d:(H + Hk) * d], qkv[:, (H + Hk) * d:]
+            else:
+                q, k, v = self.q_proj(x)[:, 0], self.k_proj(x)[:, 0], self.v_proj(x)[:, 0]
+            c, s_ = (cos[:, 0], sin[:, 0]) if cos.dim() == 3 else (cos[0], sin[0])
+            o = cache.attend(layer, q.view(B, H, d), k.view(B, Hk, d), v.view(B, Hk, d), self.scale, cos=c, sin=s_, key_valid=key_valid)
+            return self.o_proj(o.view(B, 1, H * d)), None
         if flash:
             if _is_int8(self.q_proj):
                 qkv = torch.cat((self.q_proj(x), self.k_proj(x), self.v_proj(x)), dim=-1)
@@ -215,7 +231,7 @@ class LlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = LlamaRMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
     def forward(self, hidden_states, attention_mask=None, cos=None, sin=None, key_valid=None, past_key_value=None, use_cache=False,
-                flash=False, deferred=None, defer_out=False, **unused):
+                flash=False, deferred=None, defer_out=False, static=None, **unused):
         """`deferred` / `defer_out` (otter_amd extension, used by LlamaModel.forward): the MLP output of a layer is handed to
         the NEXT layer un-added, where the residual add is fused into that layer's input RMSNorm pass (one trip over the fp32
         residual stream instead of two).  With the defaults this is exactly the reference block."""
@@ -225,8 +241,11 @@ class LlamaDecoderLayer(nn.Module):
             x, a = self.input_layernorm(x, delta=deferred, out_dtype=cd)       # x = x + mlp_out(prev) ; a = norm(x)
         else:
             a = self.input_layernorm(x, out_dtype=cd)
-        b, new_past = self.self_attn(a, cos, sin, attn_mask=attention_mask, key_valid=key_valid, past_key_value=past_key_value,
-                                     use_cache=use_cache, flash=flash)
+        if static is not None:
+            b, new_past = self.self_attn(a, cos, sin, key_valid=key_valid, static=static)
+        else:
+            b, new_past = self.self_attn(a, cos, sin, attn_mask=attention_mask, key_valid=key_valid, past_key_value=past_key_value,
+                                         use_cache=use_cache, flash=flash)
         x, m = self.post_attention_layernorm(x, delta=b, out_dtype=cd)          # x = x + b ; m = norm(x)   (one pass)
         d = self.mlp(m)
         if defer_out:
@@ -274,6 +293,37 @@ class LlamaModel(LlamaPreTrainedModel):
     def _core(layer):
         return getattr(layer, "decoder_layer", layer)   # OtterLayer wraps the decoder layer (modeling_otter.py:398-442)
 
+    def _forward_static(self, x, cache: StaticKVCache, attention_mask, position_ids):
+        """`past_key_values` is a StaticKVCache.  Empty: the prompt pass is the ordinary one (flash or SDPA), whose rotated keys and values
+        are copied into the cache once.  Filled: one token per row, every layer's attention one `cache.attend` on its projection outputs.
+        The same object comes back as `past_key_values`."""
+        B, S = x.shape[:2]
+        cache.check_step(B, S)
+        if cache.length == 0:
+            out = self.forward(inputs_embeds=x, attention_mask=attention_mask, position_ids=position_ids, past_key_values=None, use_cache=True)
+            for i, (k, v) in enumerate(out.past_key_values):
+                cache.fill(i, k, v)                          # legacy layout: k, v [B,H,S,d]
+            cache.length = S
+            return BaseModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=cache)
+        pos = cache.length
+        cos_t, sin_t = self.rotary_emb.tables(pos + 1, x.device)
+        if position_ids is None:
+            cos, sin = cos_t[pos:pos + 1], sin_t[pos:pos + 1]
+        else:
+            cos, sin = cos_t[position_ids], sin_t[position_ids]                  # [B,1,d]
+        key_valid = None
+        if attention_mask is not None:                       # (no host round trip: the kernel evaluates the mask, all-valid or not)
+            key_valid = attention_mask[:, -(pos + 1):].to(torch.uint8)
+        delta = None
+        for i, layer in enumerate(self.layers):
+            if delta is not None and getattr(layer, "gated_cross_attn_layer", None) is not None:
+                x = x + delta
+                delta = None
+            x, _, delta = layer(x, cos=cos, sin=sin, key_valid=key_valid, deferred=delta, defer_out=True, static=(cache, i))
+        _, x = self.norm(x, delta=delta, out_dtype=OF.compute_dtype_for(x))
+        cache.length = pos + 1
+        return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 use_cache=None, return_dict=True, **unused):
         if (input_ids is None) == (inputs_embeds is None):
@@ -282,6 +332,8 @@ class LlamaModel(LlamaPreTrainedModel):
         # attention path produces anyway
         use_cache = bool(use_cache) if use_cache is not None else bool(getattr(self.config, "use_cache", True))
         x = self.embed_tokens(input_ids) if inputs_embeds is None else inputs_embeds
+        if isinstance(past_key_values, StaticKVCache):
+            return self._forward_static(x, past_key_values, attention_mask, position_ids)
         B, S = x.shape[:2]
         s_past = 0
         if past_key_values is not None and len(past_key_values) and past_key_values[0] is not None and len(past_key_values[0]) == 2:

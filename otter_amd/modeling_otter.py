@@ -561,11 +561,19 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         `length_penalty` / `min_new_tokens`, temperature / top-k / top-p sampling: what the reference's demos, benchmark
         wrappers and serving code pass -- is otter_amd/generation.py (the pinned transformers' algorithm, restated).
         `use_cache` selects between the two decode modes of SURVEY.md section 3.2 (default: the LM config's use_cache, False
-        for OTTER-MPT7B)."""
-        from .generation import generate_tokens
+        for OTTER-MPT7B).  `cache_implementation="static"` (implies use_cache) keeps the keys and values in one preallocated
+        StaticKVCache (otter_amd/kv_cache.py): a step appends in place and beam search reorders an int32 table instead of the cache;
+        None or "dynamic" is the growing tuple cache."""
+        from .generation import generate_tokens, resolve_max_length
+        from .kv_cache import StaticKVCache, cache_geometry
 
         num_beams = int(generate_kwargs.get("num_beams", 1) or 1)
         use_cache = bool(generate_kwargs.pop("use_cache", getattr(self.lang_encoder.config, "use_cache", False)))
+        cache_impl = generate_kwargs.pop("cache_implementation", None)
+        if cache_impl not in (None, "dynamic", "static"):
+            raise ValueError("generate: cache_implementation must be None, 'dynamic' or 'static', got %r" % (cache_impl,))
+        static = cache_impl == "static"
+        use_cache = use_cache or static
         generate_kwargs.setdefault("eos_token_id", self.eoc_token_id)
         self._encode_vision_x(vision_x=vision_x)
         if num_beams > 1:   # perceiver output repeated per beam: same conditioning as encoding the repeated frames, 1/num_beams the work
@@ -574,7 +582,22 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
                     layer.condition_vis_x(layer.vis_x.repeat_interleave(num_beams, dim=0))
         lm = self.lang_encoder
 
+        def new_static_cache(ids):
+            n_layers, n_kv, head_dim, host_max = cache_geometry(lm.config)
+            max_len = min(resolve_max_length(lang_x.shape[1], generate_kwargs.get("max_new_tokens"), generate_kwargs.get("max_length")), host_max)
+            emb = lm.get_input_embeddings().weight
+            return StaticKVCache(n_layers, ids.shape[0], n_kv, head_dim, max(max_len, ids.shape[1] + 1), emb.device, OF.compute_dtype_for(emb))
+
         def step(ids, mask, past, beam_idx):
+            if static:
+                if past is None:                             # rows = sentences x beams: generate_tokens has repeated the prompt already
+                    return_ids, past = ids, new_static_cache(ids)
+                else:
+                    if beam_idx is not None:
+                        past.reorder(beam_idx)               # the table moves, the cache does not
+                    return_ids = ids[:, -1:]
+                out = lm(input_ids=return_ids, attention_mask=mask, past_key_values=past, use_cache=True)
+                return out.logits[:, -1, :], past
             if use_cache and past is not None:
                 if beam_idx is not None:
                     past = [tuple(t.index_select(0, beam_idx) for t in layer) for layer in past]   # a list: the MPT host fills it in place

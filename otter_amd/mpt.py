@@ -22,6 +22,7 @@ from transformers import PretrainedConfig, PreTrainedModel
 from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
 
 from . import functional as OF
+from .kv_cache import StaticKVCache
 
 _ATTN_DEFAULTS = dict(attn_type="multihead_attention", attn_pdrop=0.0, attn_impl="torch", qk_ln=False, clip_qkv=None,
                       softmax_scale=None, prefix_lm=False, attn_uses_sequence_id=False, alibi=True, alibi_bias_max=8)
@@ -279,10 +280,17 @@ class MultiheadAttention(nn.Module):
         self.Wqkv = FrozenAwareLinear(d_model, 3 * d_model, bias=bias)
         self.out_proj = FrozenAwareLinear(d_model, d_model, bias=bias)
 
-    def forward(self, x, past_key_value=None, attn_bias=None, is_causal=True, flash=None, decode=None):
+    def forward(self, x, past_key_value=None, attn_bias=None, is_causal=True, flash=None, decode=None, static=None):
         B, S, D = x.shape
         H, d = self.n_heads, D // self.n_heads
         qkv = self.Wqkv(x)
+        if static is not None:
+            # cached step over a StaticKVCache (otter_amd/kv_cache.py; csrc/decode_cache.hip on the GPU in bf16 at head_dim 128): q, k, v are
+            # the three slices of the projection row, read in place; the cache is appended in place and read through its beam table
+            cache, layer, slopes, key_valid = static
+            q4 = qkv.view(B, 3, H, d)
+            o = cache.attend(layer, q4[:, 0], q4[:, 1], q4[:, 2], self.softmax_scale, key_valid=key_valid, slopes=slopes)
+            return self.out_proj(o.view(B, 1, D)), None
         if decode is not None and past_key_value is not None and len(past_key_value) != 0 and S == 1:
             # cached decode step on HIP (csrc/decode.hip): the new key / value are appended to the cache in the reference's
             # layout (k [B,H,d,S], v [B,H,S,d]) and the single query attends over it in place -- no SDPA, no [B,H,1,S] bias tensor
@@ -329,7 +337,7 @@ class MPTBlock(nn.Module):
         self.ffn = MPTMLP(config.d_model, config.expansion_ratio, bias)
 
     def forward(self, x, past_key_value=None, attn_bias=None, attention_mask=None, is_causal=True, deferred=None,
-                defer_out=False, flash=None, decode=None, fork_input=False):
+                defer_out=False, flash=None, decode=None, fork_input=False, static=None):
         """`deferred` / `defer_out` (otter_amd extension, used by MPTModel.forward): the FFN output of a block is handed to
         the NEXT block un-added, where the residual add is fused into that block's norm_1 pass (one trip over the fp32
         residual stream instead of two).  With the defaults this is exactly mpt/blocks.py:68-88."""
@@ -339,7 +347,10 @@ class MPTBlock(nn.Module):
             x, a = self.norm_1.fork_forward(x)            # same values; the stream's two gradients meet inside the LayerNorm backward
         else:
             a = self.norm_1(x)
-        b, past_key_value = self.attn(a, past_key_value=past_key_value, attn_bias=attn_bias, is_causal=is_causal, flash=flash, decode=decode)
+        if static is not None:
+            b, past_key_value = self.attn(a, static=static)
+        else:
+            b, past_key_value = self.attn(a, past_key_value=past_key_value, attn_bias=attn_bias, is_causal=is_causal, flash=flash, decode=decode)
         x, m = self.norm_2.add_forward(x, b)              # x = x + b ; m = norm_2(x)
         n = self.ffn(m)
         if defer_out:
@@ -441,6 +452,37 @@ class MPTModel(MPTPreTrainedModel):
             self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
         return self._slopes.float().contiguous(), key_valid
 
+    def _forward_static(self, input_ids, cache: StaticKVCache, attention_mask):
+        """`past_key_values` is a StaticKVCache.  Empty: the prompt pass is the ordinary one (flash or SDPA), whose keys / values are copied
+        into the cache once.  Filled: one token per row, every block's attention one `cache.attend` on its projection output -- no cat, no
+        view of the past, no additive mask tensor.  The same object comes back as `past_key_values`."""
+        B, S = input_ids.shape
+        cache.check_step(B, S)
+        if cache.length == 0:
+            out = self.forward(input_ids, past_key_values=None, attention_mask=attention_mask, use_cache=True)
+            for i, (k, v) in enumerate(out.past_key_values):
+                cache.fill(i, k.transpose(2, 3), v)          # legacy layout: k [B,H,d,S], v [B,H,S,d]
+            cache.length = S
+            return BaseModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=cache)
+        x = self.wte(input_ids)
+        pos = cache.length
+        if self._slopes is None or self._slopes.device != x.device:
+            self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
+        slopes = self._slopes.float().contiguous()          # (fp32 and contiguous already: no copy)
+        key_valid = None
+        if attention_mask is not None:                       # (no host round trip: the kernel evaluates the mask, all-valid or not)
+            key_valid = attention_mask[:, -(pos + 1):].to(torch.uint8)
+        delta = None
+        for i, block in enumerate(self.blocks):
+            if delta is not None and getattr(block, "gated_cross_attn_layer", None) is not None and not _gated_takes_deferred(block, x, delta):
+                x = x + delta
+                delta = None
+            out = block(x, deferred=delta, defer_out=True, static=(cache, i, slopes, key_valid))
+            x, delta = out[0], out[3]
+        _, x = self.norm_f.add_forward(x, delta)
+        cache.length = pos + 1
+        return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
+
     def forward(self, input_ids, past_key_values=None, attention_mask=None, use_cache=None, return_dict=True, **unused):
         use_cache = use_cache if use_cache is not None else self.config.use_cache
         if attention_mask is not None and self.training and int(attention_mask[:, 0].sum()) != attention_mask.shape[0]:
@@ -448,6 +490,8 @@ class MPTModel(MPTPreTrainedModel):
         S = input_ids.size(1)
         if S > self.config.max_seq_len:
             raise ValueError(f"Cannot forward input with seq_len={S}, this model only supports seq_len<={self.config.max_seq_len}")
+        if isinstance(past_key_values, StaticKVCache):
+            return self._forward_static(input_ids, past_key_values, attention_mask)
         x = self.wte(input_ids)
         s_past = 0
         if past_key_values is not None and len(past_key_values) and len(past_key_values[0]) != 0:

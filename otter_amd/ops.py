@@ -537,7 +537,67 @@ def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past,
     return o, k_new, v_new
 
 
-GEMV_W8_MAX_ROWS = 16                  # include/otter_hip.h: 1 <= M <= 16
+DECODE_CACHED_MAX_KEYS = 65536         # include/otter_hip.h: S_max <= 65536
+
+
+def decode_attn_cached_workspace_bytes(N: int, H: int, Sk: int) -> int:
+    """OTTER_DECODE_CACHED_WORKSPACE_BYTES of include/otter_hip.h."""
+    return N * H * ((Sk + 127) // 128) * 130 * 4
+
+
+def _decode_new_ok(t, N, H) -> bool:
+    return (t.dtype == torch.bfloat16 and t.dim() == 3 and tuple(t.shape) == (N, H, 128) and t.stride(2) == 1 and t.stride(0) % 8 == 0
+            and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0)
+
+
+def decode_attn_cached(q, k_new, v_new, k_cache, v_cache, pos, scale, cos=None, sin=None, src=None, key_valid=None, slopes=None):
+    """One cached decode step over a static cache (otter_decode_attn_cached).  q / k_new / v_new bf16 [N,H,128] views (unit dim stride,
+    strides % 8 == 0, 16-B aligned: slices of a fused projection row or separate projection outputs, read in place); k_cache / v_cache bf16
+    [N,H,S_max,128] with key stride 128, written in place at slot `pos` (1 <= pos < S_max) of every row; cos / sin fp32 [128] or [N,128]
+    rows of position `pos` (both or neither: rotate_half rotary on q and k_new); src int32 [N, >= pos] (row stride free) or None;
+    key_valid uint8 [N, >= pos+1] or None; slopes fp32 [H] or None.  Returns o [N,H*128] bf16."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, cos, sin, src, key_valid, slopes)
+    if q.dim() != 3:
+        raise K.OtterHipError("decode_attn_cached: q must be [N,H,128]")
+    N, H = q.shape[:2]
+    if not (_decode_new_ok(q, N, H) and _decode_new_ok(k_new, N, H) and _decode_new_ok(v_new, N, H)):
+        raise K.OtterHipError("decode_attn_cached: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
+    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
+    for t in (k_cache, v_cache):
+        if (t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 128) or t.stride(3) != 1 or t.stride(2) != 128
+                or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < S_max * 128 or t.data_ptr() % 16):
+            raise K.OtterHipError("decode_attn_cached: k_cache / v_cache must be bf16 [N,H,S_max,128] with key stride 128, unit dim stride, 16-B aligned")
+    pos = int(pos)
+    if S_max > DECODE_CACHED_MAX_KEYS or pos < 1 or pos >= S_max:
+        raise K.OtterHipError(f"decode_attn_cached: pos={pos} outside [1, S_max) with S_max={S_max} (limit {DECODE_CACHED_MAX_KEYS})")
+    if (cos is None) != (sin is None):
+        raise K.OtterHipError("decode_attn_cached: cos and sin must both be given or both be None")
+    cs_stride = 0
+    if cos is not None:
+        for t in (cos, sin):
+            if (t.dtype != torch.float32 or t.shape[-1] != 128 or t.stride(-1) != 1 or tuple(t.shape) not in ((128,), (N, 128))
+                    or tuple(t.shape) != tuple(cos.shape) or t.stride() != cos.stride()):
+                raise K.OtterHipError("decode_attn_cached: cos / sin must be fp32 [128] or [N,128] with a unit dim stride and equal strides")
+        cs_stride = cos.stride(0) if cos.dim() == 2 else 0
+    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < pos or src.stride(1) != 1):
+        raise K.OtterHipError("decode_attn_cached: src must be int32 [N, >= pos] with a unit column stride")
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < pos + 1
+                                  or key_valid.stride(1) != 1):
+        raise K.OtterHipError("decode_attn_cached: key_valid must be uint8 [N, >= pos+1] with a unit column stride")
+    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
+        raise K.OtterHipError("decode_attn_cached: slopes must be contiguous fp32 [H]")
+    o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
+    ws = _ws.get(decode_attn_cached_workspace_bytes(N, H, pos + 1), q.device)
+    K.check(K.lib().otter_decode_attn_cached(
+        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
+        v_new.stride(1), K.ptr(cos), K.ptr(sin), cs_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(),
+        v_cache.stride(0), v_cache.stride(1), K.ptr(src), src.stride(0) if src is not None else 0, K.ptr(key_valid),
+        key_valid.stride(0) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 128,
+        float(scale), K.stream()), "decode_attn_cached")
+    return o
+
+
+GEMV_W8_MAX_ROWS = 16                 # include/otter_hip.h: 1 <= M <= 16
 
 
 def gemv_w8_workspace_bytes(M: int, N: int, K: int) -> int:
