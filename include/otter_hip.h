@@ -397,6 +397,23 @@ int otter_decode_attn_cached(const void* q, int64_t q_row_stride, int64_t q_head
                              int64_t S_max, int64_t head_dim, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_xattn_decode -- the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
+ * head_dim 64: N rows (batch x beams) of ONE query each attend over the projected media of their sentence.
+ *   q        bf16 [N, H * 64] with a row stride (elements, a multiple of 8, >= H * 64), 16-byte aligned.
+ *   k / v    bf16 views [sentences, M, H * 64] of one buffer with a shared row stride (a multiple of 8, >= H * 64; the sentence stride
+ *            is M * kv_stride), 16-byte aligned.  M = T_img * n_per_media <= 65536; the media index of key j is j / n_per_media.
+ *   the media of row r are sentence r / rows_per_media (rows_per_media = the beams of a sentence; N a multiple of it).
+ *   text_time  int32 [N].  mask_mode EQ or GE (OTTER_MASK_NONE is rejected: a decode step always has a text_time).
+ *   o        bf16 [N, H * 64] contiguous.
+ * Semantics are those of otter_attn_fwd for a Tq = 1 row: masked scores take -FLT_MAX, a row whose every key is masked comes out
+ * uniform (1/M over all keys), a row with text_time == 0 is zeroed in EQ mode only.  In EQ mode with 1 <= text_time <= T_img only
+ * the n_per_media keys of that media are read.  No workspace, no atomics; two calls on the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------------- */
+int otter_xattn_decode(const void* q, int64_t q_stride, const void* k, const void* v, int64_t kv_stride, const int32_t* text_time, void* o,
+                       int64_t N, int64_t H, int64_t T_img, int64_t n_per_media, int64_t rows_per_media, int mask_mode, float scale,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Int8 weight-only products of the frozen decoder during generation (the reference's serving worker offers load_in_8bit for the
  * same model: pipeline/serve/model_worker.py:92-94).  Format: qweight int8 [N, K] row-major with row stride ldw, scale fp32 [N]:
  * scale[n] = max_k |W[n,k]| / 127 (1 for an all-zero row), q[n,k] = clamp(round_half_even(W[n,k] / scale[n]), -127, 127).

@@ -222,6 +222,46 @@ class OtterGatedCrossAttentionBlock(nn.Module):
                                               a.to_kv.weight, a.to_out.weight, self.attn_gate, ff[0].weight, ff[0].bias,
                                               ff[1].weight, ff[3].weight, self.ff_gate, deferred)
 
+    @torch.no_grad()
+    def decode_step(self, x, cache, layer_index: int, deferred=None):
+        """One cached step over a MediaCache (otter_amd/media_cache.py): x [rows, 1, D], the step's text_time and this layer's projected media
+        come from `cache`.  The launch sequence of GatedCrossAttentionFn.forward with the same ops and epilogues, minus the media cast, the
+        `to_kv` product and the side stream they ran on, and with csrc/xattn_decode.hip in place of the 64-row-tile attention kernel:
+        (add+)LayerNorm -> to_q -> xattn_decode -> to_out (scale + residual tail) -> LayerNorm -> FF up (GELU tail) -> FF down (scale +
+        residual tail).  On the CPU / in fp32 compute: the same sequence in plain torch around `MediaCache.attend_reference`."""
+        a, ff = self.attn, self.feed_forward
+        N, S, D = x.shape
+        if S != 1:
+            raise ValueError("decode_step: one token per row (got %d)" % S)
+        cd, rd = OF.compute_dtype_for(x), x.dtype
+        x2 = x.reshape(N, D).contiguous()
+        d2 = deferred.reshape(N, D).contiguous() if deferred is not None else None
+        if x.is_cuda and cd == torch.bfloat16:
+            w = OF.shadows.w
+            ga, gf = OF._flat_gate(self.attn_gate), OF._flat_gate(self.ff_gate)
+            nw, nb = a.norm.weight.detach(), a.norm.bias.detach()
+            if d2 is not None:
+                x2, xn, _, _ = ops.add_layernorm_fwd(x2, d2, nw, nb, cd, a.norm.eps, need_stats=False)
+            else:
+                xn = ops.layernorm_fwd(x2, nw, nb, cd, a.norm.eps, need_stats=False)[0]
+            q = ops.gemm_nt(xn, w(a.to_q.weight, cd))
+            o = cache.attend(layer_index, q)
+            x1 = ops.gemm_nt(o, w(a.to_out.weight, cd), out_dtype=rd, kind=OF.EPI_SCALE_RES, gate=ga, R=x2)       # attn*tanh(g)+x
+            f = ops.layernorm_fwd(x1, ff[0].weight.detach(), ff[0].bias.detach(), cd, ff[0].eps, need_stats=False)[0]
+            h = ops.gemm_nt(f, w(ff[1].weight, cd), kind=OF.EPI_GELU)
+            y = ops.gemm_nt(h, w(ff[3].weight, cd), out_dtype=rd, kind=OF.EPI_SCALE_RES, gate=gf, R=x1)           # ff*tanh(g)+x1
+            return y.view(N, 1, D)
+        F = torch.nn.functional
+        if d2 is not None:
+            x2 = x2 + d2.to(rd)
+        lin = lambda t, W: F.linear(t, W.detach().to(cd))
+        xn = F.layer_norm(x2.float(), (D,), a.norm.weight.float(), a.norm.bias.float(), a.norm.eps).to(cd)
+        o = cache.attend(layer_index, lin(xn, a.to_q.weight))
+        x1 = (lin(o, a.to_out.weight).float() * torch.tanh(self.attn_gate.float()) + x2.float()).to(rd)
+        f = F.layer_norm(x1.float(), (D,), ff[0].weight.float(), ff[0].bias.float(), ff[0].eps).to(cd)
+        y = (lin(F.gelu(lin(f, ff[1].weight)), ff[3].weight).float() * torch.tanh(self.ff_gate.float()) + x1.float()).to(rd)
+        return y.view(N, 1, D)
+
 
 class OtterLayer(nn.Module):
     def __init__(self, gated_cross_attn_layer: nn.Module, decoder_layer: nn.Module):
@@ -232,6 +272,7 @@ class OtterLayer(nn.Module):
         self.media_locations = None
         self.attend_previous = None
         self.text_time = None
+        self.media_step = None
 
     def is_conditioned(self) -> bool:
         return self.vis_x is not None
@@ -250,6 +291,10 @@ class OtterLayer(nn.Module):
         """otter_amd extension: the media-time scan is shared by all layers instead of being recomputed per layer."""
         self.text_time = text_time
 
+    def condition_media_step(self, media_step) -> None:
+        """otter_amd extension: (MediaCache, this layer's index) for ONE cached step over a media cache, or None (every other forward)."""
+        self.media_step = media_step
+
     def forward(self, lang_x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, **decoder_layer_kwargs):
         if self.gated_cross_attn_layer is None:
             return self.decoder_layer(lang_x, attention_mask=attention_mask, **decoder_layer_kwargs)
@@ -262,8 +307,11 @@ class OtterLayer(nn.Module):
         # carries on (`fork_input`: one LayerNorm-backward pass instead of an extra gradient add)
         deferred = decoder_layer_kwargs.pop("deferred", None)
         gkw = {"deferred": deferred} if deferred is not None else {}
-        lang_x = self.gated_cross_attn_layer(lang_x, self.vis_x, media_locations=self.media_locations,
-                                             attend_previous=self.attend_previous, text_time=self.text_time, **gkw)
+        if self.media_step is not None:
+            lang_x = self.gated_cross_attn_layer.decode_step(lang_x, *self.media_step, **gkw)
+        else:
+            lang_x = self.gated_cross_attn_layer(lang_x, self.vis_x, media_locations=self.media_locations,
+                                                 attend_previous=self.attend_previous, text_time=self.text_time, **gkw)
         if "defer_out" in decoder_layer_kwargs:       # (only otter_amd's MPTBlock takes the extension keywords)
             decoder_layer_kwargs["fork_input"] = True
         return self.decoder_layer(lang_x, attention_mask=attention_mask, **decoder_layer_kwargs)
@@ -297,15 +345,40 @@ class OtterLMMixin(nn.Module):
         """Condition the Otter layers on the media locations before forward()."""
         if not getattr(self, "initialized_otter", False):
             raise ValueError("Otter layers are not initialized. Please call `init_otter` first.")
+        media_cache = kwargs.pop("media_cache", None)
         input_ids = kwargs["input_ids"] if "input_ids" in kwargs else input[0]
         media_locations = input_ids == self.media_token_id
+        layers = self._get_decoder_layers()
+        if media_cache is not None:
+            media_cache.check_step(input_ids.shape[0], input_ids.shape[1], self.use_media_placement_augmentation)
+            if media_cache.filled:
+                return self._forward_media_step(media_cache, media_locations, input, kwargs)
         attend_previous = (random.random() < 0.5) if self.use_media_placement_augmentation else True
         tt = ops.text_time(media_locations, attend_previous)
-        for layer in self._get_decoder_layers():
+        for layer in layers:
             layer.condition_media_locations(media_locations)
             layer.condition_attend_previous(attend_previous)
             layer.condition_text_time(tt)
-        return super().forward(*input, **kwargs)
+        out = super().forward(*input, **kwargs)
+        if media_cache is not None:          # the prompt pass was the ordinary forward; the cache takes the counts and the projected media
+            media_cache.fill(media_locations, layers)
+        return out
+
+    def _forward_media_step(self, media_cache, media_locations, input, kwargs):
+        """One cached step over a filled MediaCache (otter_amd/media_cache.py): the running <image> count is advanced on the device and is the
+        text_time of every gated layer, whose blocks run `decode_step` on the cached media projections."""
+        layers = self._get_decoder_layers()
+        tt = media_cache.advance(kwargs["input_ids"] if "input_ids" in kwargs else input[0])
+        try:
+            for i, layer in enumerate(layers):
+                layer.condition_media_locations(media_locations)
+                layer.condition_attend_previous(True)
+                layer.condition_text_time(tt.view(-1, 1))
+                layer.condition_media_step((media_cache, i))
+            return super().forward(*input, **kwargs)
+        finally:
+            for layer in layers:
+                layer.condition_media_step(None)
 
     def is_conditioned(self) -> bool:
         return all(l.is_conditioned() for l in self._get_decoder_layers())
@@ -315,6 +388,7 @@ class OtterLMMixin(nn.Module):
             layer.condition_vis_x(None)
             layer.condition_media_locations(None)
             layer.condition_attend_previous(None)
+            layer.condition_media_step(None)
 
 
 # ======================================================================================================================
@@ -563,9 +637,13 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         `use_cache` selects between the two decode modes of SURVEY.md section 3.2 (default: the LM config's use_cache, False
         for OTTER-MPT7B).  `cache_implementation="static"` (implies use_cache) keeps the keys and values in one preallocated
         StaticKVCache (otter_amd/kv_cache.py): a step appends in place and beam search reorders an int32 table instead of the cache;
-        None or "dynamic" is the growing tuple cache."""
+        None or "dynamic" is the growing tuple cache.  `cross_attention_cache=True` (needs a cached mode) makes every cached step return
+        what the last position of the full re-forward returns: a MediaCache (otter_amd/media_cache.py) carries each row's <image> count and
+        the projected media, so the step attends to the image instead of reproducing the reference's zero; without it every path is
+        unchanged."""
         from .generation import generate_tokens, resolve_max_length
         from .kv_cache import StaticKVCache, cache_geometry
+        from .media_cache import MediaCache
 
         num_beams = int(generate_kwargs.get("num_beams", 1) or 1)
         use_cache = bool(generate_kwargs.pop("use_cache", getattr(self.lang_encoder.config, "use_cache", False)))
@@ -574,6 +652,11 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             raise ValueError("generate: cache_implementation must be None, 'dynamic' or 'static', got %r" % (cache_impl,))
         static = cache_impl == "static"
         use_cache = use_cache or static
+        media = [None]                                       # the MediaCache of this call, created beside the KV cache
+        if bool(generate_kwargs.pop("cross_attention_cache", False)):
+            if not use_cache:
+                raise ValueError("generate: cross_attention_cache=True needs use_cache=True or cache_implementation='static'")
+            media[0] = False                                 # (wanted, not created yet)
         generate_kwargs.setdefault("eos_token_id", self.eoc_token_id)
         self._encode_vision_x(vision_x=vision_x)
         if num_beams > 1:   # perceiver output repeated per beam: same conditioning as encoding the repeated frames, 1/num_beams the work
@@ -588,7 +671,17 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             emb = lm.get_input_embeddings().weight
             return StaticKVCache(n_layers, ids.shape[0], n_kv, head_dim, max(max_len, ids.shape[1] + 1), emb.device, OF.compute_dtype_for(emb))
 
+        def media_kw(ids, past, beam_idx):
+            if media[0] is None:
+                return {}
+            if past is None:
+                media[0] = MediaCache(ids.shape[0], self.media_token_id, rows_per_media=num_beams)
+            elif beam_idx is not None:
+                media[0].reorder(beam_idx)
+            return {"media_cache": media[0]}
+
         def step(ids, mask, past, beam_idx):
+            mkw = media_kw(ids, past, beam_idx)
             if static:
                 if past is None:                             # rows = sentences x beams: generate_tokens has repeated the prompt already
                     return_ids, past = ids, new_static_cache(ids)
@@ -596,14 +689,14 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
                     if beam_idx is not None:
                         past.reorder(beam_idx)               # the table moves, the cache does not
                     return_ids = ids[:, -1:]
-                out = lm(input_ids=return_ids, attention_mask=mask, past_key_values=past, use_cache=True)
+                out = lm(input_ids=return_ids, attention_mask=mask, past_key_values=past, use_cache=True, **mkw)
                 return out.logits[:, -1, :], past
             if use_cache and past is not None:
                 if beam_idx is not None:
                     past = [tuple(t.index_select(0, beam_idx) for t in layer) for layer in past]   # a list: the MPT host fills it in place
-                out = lm(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True)
+                out = lm(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True, **mkw)
             else:
-                out = lm(input_ids=ids, attention_mask=mask, use_cache=use_cache)
+                out = lm(input_ids=ids, attention_mask=mask, use_cache=use_cache, **mkw)
             return out.logits[:, -1, :], (out.past_key_values if use_cache else None)
 
         try:

@@ -597,6 +597,48 @@ def decode_attn_cached(q, k_new, v_new, k_cache, v_cache, pos, scale, cos=None, 
     return o
 
 
+XATTN_DECODE_MAX_KEYS = 65536          # include/otter_hip.h: M = T_img * n_per_media <= 65536
+
+
+def xattn_decode(q, k, v, H, text_time, n_per_media, rows_per_media, mask_mode, scale, out=None):
+    """The masked cross-attention core of one cached step over a media cache (otter_xattn_decode).  q bf16 [N, H*64] (row stride free, % 8);
+    k, v bf16 [sentences, M, H*64] views of one buffer (shared row stride % 8, sentence stride M * row stride; usually the two halves of a
+    to_kv output); row r reads sentence r // rows_per_media; text_time int32 [N]; mask_mode EQ or GE.  Returns o [N, H*64] bf16 (`out`:
+    a contiguous bf16 [N, H*64] tensor to write instead)."""
+    K.require_cuda(q, k, v, text_time, out)
+    if q.dim() != 2 or k.dim() != 3 or v.dim() != 3 or k.shape != v.shape:
+        raise K.OtterHipError("xattn_decode: q must be [N, H*64], k and v [sentences, M, H*64] of equal shape")
+    N, HD = q.shape
+    S, M = k.shape[:2]
+    n_per_media, rows_per_media = int(n_per_media), int(rows_per_media)
+    if HD != H * 64 or k.shape[2] != HD:
+        raise K.OtterHipError(f"xattn_decode: head_dim 64 only (q inner={HD}, k inner={k.shape[2]}, heads={H})")
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise K.OtterHipError("xattn_decode: q, k, v must be bf16")
+    if n_per_media < 1 or M < 1 or M % n_per_media != 0 or M > XATTN_DECODE_MAX_KEYS:
+        raise K.OtterHipError(f"xattn_decode: M={M} must be a positive multiple of n_per_media={n_per_media}, at most {XATTN_DECODE_MAX_KEYS}")
+    if rows_per_media < 1 or N != S * rows_per_media:
+        raise K.OtterHipError(f"xattn_decode: N={N} rows need {S} sentences x rows_per_media={rows_per_media}")
+    if q.stride(1) != 1 or k.stride(2) != 1 or v.stride(2) != 1 or k.stride(1) != v.stride(1) or q.stride(0) % 8 or k.stride(1) % 8:
+        raise K.OtterHipError("xattn_decode: unit dim strides, a shared k / v row stride, row strides % 8 == 0")
+    if q.stride(0) < HD or k.stride(1) < HD or (S > 1 and (k.stride(0) != M * k.stride(1) or v.stride(0) != M * v.stride(1))):
+        raise K.OtterHipError("xattn_decode: row strides >= H*64 and a sentence stride of M * row stride")
+    if q.data_ptr() % 16 or k.data_ptr() % 16 or v.data_ptr() % 16:
+        raise K.OtterHipError("xattn_decode: q, k, v must be 16-byte aligned")
+    if text_time.dtype != torch.int32 or tuple(text_time.shape) != (N,) or not text_time.is_contiguous():
+        raise K.OtterHipError("xattn_decode: text_time must be contiguous int32 [N]")
+    if mask_mode not in (MASK_EQ, MASK_GE):
+        raise K.OtterHipError(f"xattn_decode: mask_mode {mask_mode} (EQ or GE only)")
+    if out is None:
+        out = torch.empty((N, HD), dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, HD) or not out.is_contiguous():
+        raise K.OtterHipError("xattn_decode: out must be a contiguous bf16 [N, H*64] tensor")
+    K.check(K.lib().otter_xattn_decode(q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(1), text_time.data_ptr(), out.data_ptr(),
+                                       N, H, M // n_per_media, n_per_media, rows_per_media, int(mask_mode), float(scale), K.stream()),
+            "xattn_decode")
+    return out
+
+
 GEMV_W8_MAX_ROWS = 16                 # include/otter_hip.h: 1 <= M <= 16
 
 
