@@ -397,6 +397,31 @@ int otter_decode_attn_cached(const void* q, int64_t q_row_stride, int64_t q_head
                              int64_t S_max, int64_t head_dim, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_decode_attn_cached_dyn -- otter_decode_attn_cached with the position in DEVICE memory: nothing in the launch (grid, workspace
+ * size, scalar arguments) depends on it, so one captured launch can be replayed at every position of a generate() call.
+ *   pos_dev  const int32 [1] in device memory, 4-byte aligned: read by the kernel.  A value outside [1, S_max) makes the call a no-op
+ *            (o and the cache are left untouched): a corrupt counter never indexes the cache.
+ *   cos_table / sin_table  fp32 [>= S_max, 128] with a row stride >= 128 (elements), or both NULL: the kernel takes row pos itself,
+ *            shared by every n.
+ *   src      int32 [N, >= S_max - 1], key_valid uint8 [N, >= S_max] with row strides: columns < pos (src) and <= pos (key_valid) are
+ *            read, as in the scalar entry point, but any position below S_max may come up.
+ *   workspace  at least OTTER_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max) bytes.
+ * Everything else is as in otter_decode_attn_cached.  The grid covers the most key ranges any position below S_max can have; the
+ * ranges of the current position come from the same rule as the scalar entry point's, a workgroup whose range is not live returns
+ * before it touches memory, and the live ranges are combined in range order: at every pos, o and the written cache slot are
+ * bit-identical to otter_decode_attn_cached called with that pos.  The entry point validates before it launches, allocates nothing,
+ * does not synchronise, and queries the device only for its CU count, once per device (call it once outside a stream capture).
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(S_max) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                 int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                 const float* cos_table, const float* sin_table, int64_t table_row_stride, void* k_cache,
+                                 int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                 int64_t v_cache_head_stride, const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid,
+                                 int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes,
+                                 int64_t N, int64_t H, const int32_t* pos_dev, int64_t S_max, int64_t head_dim, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * otter_xattn_decode -- the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
  * head_dim 64: N rows (batch x beams) of ONE query each attend over the projected media of their sentence.
  *   q        bf16 [N, H * 64] with a row stride (elements, a multiple of 8, >= H * 64), 16-byte aligned.

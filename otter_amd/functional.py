@@ -199,6 +199,25 @@ def _wgrad(dyT: torch.Tensor, xT: torch.Tensor, gate=None, param=None):
     return ops.gemm_nt(dyT, xT, out_dtype=torch.float32, kind=EPI_STORE, gate=gate)
 
 
+# Set while a decode step is captured into a graph (single_chain below): a captured step is ONE chain of launches on ONE stream, so
+# every _SideStream created meanwhile reports disabled and its work stays on the current stream.
+_single_chain = False
+
+
+class single_chain:
+    """Context: no side stream is forked inside (generate(..., graph_decode=True) wraps its capture in it)."""
+
+    def __enter__(self):
+        global _single_chain
+        self.prev, _single_chain = _single_chain, True
+        return self
+
+    def __exit__(self, *exc):
+        global _single_chain
+        _single_chain = self.prev
+        return False
+
+
 class _SideStream:
     """A second HIP stream per device for the HALF-CHIP launches of the fusion modules (round 4).  The skinny projections of a gated block
     (to_q, dO, dWo, dWq: 4096 x 512 x 4096 in some order) are 128 workgroups of one workgroup per CU: half of the MI355X's 256 CUs idle for
@@ -211,7 +230,7 @@ class _SideStream:
     _streams = {}
 
     def __init__(self, device):
-        self.enabled = device.type == "cuda" and os.environ.get("OTTER_NO_SIDE_STREAM") != "1"
+        self.enabled = device.type == "cuda" and not _single_chain and os.environ.get("OTTER_NO_SIDE_STREAM") != "1"
         self.forked = False
         if self.enabled:
             key = device.index if device.index is not None else torch.cuda.current_device()

@@ -464,6 +464,9 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
                                       "fused q/k LayerNorm + partial rotary): use the default cache, whose step runs on csrc/persimmon_decode.hip")
         if cache_impl not in (None, "dynamic"):
             raise ValueError("generate: cache_implementation must be None, 'dynamic' or 'static', got %r" % (cache_impl,))
+        if generate_kwargs.pop("graph_decode", False):
+            raise NotImplementedError("FuyuForCausalLM.generate: graph_decode=True replays a step over the static cache, which is not built "
+                                      "for the Persimmon host")
         L0 = input_ids.shape[1]
         nb = int(generate_kwargs.get("num_beams", 1) or 1)
         patches, idx0 = image_patches, image_patches_indices

@@ -13,6 +13,15 @@ instead of the cache:
               writes the new position into its OWN row, whatever its ancestry, so no slot is ever written twice and a slot that other
               rows still point at is never overwritten.
 
+Replay mode (`enable_replay`, once, after the prefill; `generate(..., graph_decode=True)`): everything a step reads that changes from step to
+step lives at a fixed device address, so that one captured graph of the step can be replayed at every position:
+
+    pos_dev   int32 [1] on the device, equal to `length`; `advance()` increments both (the device add is the last op of the captured step).
+    valid     uint8 [rows, max_len]: the prompt's attention mask in columns [0, S), ones after it (generation only ever appends ones).
+    src       created eagerly when beams are in use, so that its address and the NULL / non-NULL choice are fixed before capture.
+
+In that mode the step runs on `ops.decode_attn_cached_dyn`, which reads the position, the rotary table row and the mask columns itself.
+
 The cached step runs on csrc/decode_cache.hip (`ops.decode_attn_cached`) on the GPU in bf16 with head_dim 128 and as many key / value heads
 as query heads.  Everywhere else -- the CPU, fp32 compute, other head sizes -- `attend_reference` runs: a plain-torch restatement of exactly
 what the kernel does.  Like `Int8FrozenLinear`'s, that branch is a deliberate exception to "no PyTorch path": it is what makes the bookkeeping
@@ -50,6 +59,9 @@ class StaticKVCache:
         self.v = torch.zeros(shape, dtype=dtype, device=device)
         self.length = 0
         self.src: Optional[torch.Tensor] = None
+        self.pos_dev: Optional[torch.Tensor] = None     # replay mode (enable_replay)
+        self.valid: Optional[torch.Tensor] = None
+        self.kernel_steps = True        # replay mode: every `attend` so far ran on the dyn kernel (what a captured step needs)
 
     # ---- bookkeeping ----------------------------------------------------------------------------------------------------------------
 
@@ -93,10 +105,52 @@ class StaticKVCache:
         self.k[layer, :, :, :S].copy_(k)
         self.v[layer, :, :, :S].copy_(v)
 
+    # ---- replay mode -----------------------------------------------------------------------------------------------------------------
+
+    @property
+    def replay(self) -> bool:
+        return self.pos_dev is not None
+
+    def enable_replay(self, attention_mask: Optional[torch.Tensor] = None, beams: bool = False) -> None:
+        """Once, after the prefill: move what a step reads to fixed device addresses (module docstring).  `attention_mask` [rows, length]
+        is the prompt's mask or None (all valid); `beams`: `reorder` will be called, so the table is created now."""
+        if self.replay:
+            raise ValueError("StaticKVCache.enable_replay: replay mode is enabled already")
+        if self.length < 1:
+            raise ValueError("StaticKVCache.enable_replay: the cache is empty (the prompt pass fills it)")
+        if attention_mask is not None and tuple(attention_mask.shape) != (self.rows, self.length):
+            raise ValueError("StaticKVCache.enable_replay: attention_mask must be [%d, %d], got %s"
+                             % (self.rows, self.length, tuple(attention_mask.shape)))
+        self.valid = torch.ones((self.rows, self.max_len), dtype=torch.uint8, device=self.device)
+        if attention_mask is not None:
+            self.valid[:, :self.length] = attention_mask.to(self.device).ne(0).to(torch.uint8)
+        if beams and self.src is None:
+            self.src = self._own_rows()
+        self.pos_dev = torch.full((1,), self.length, dtype=torch.int32, device=self.device)
+
+    def advance(self) -> None:
+        """The end of a replay-mode step: the device position and the host length move together (the device add is one tiny op, the last of
+        a captured step; a graph replay runs it again, and `note_replay` moves the host side)."""
+        if not self.replay:
+            raise ValueError("StaticKVCache.advance: replay mode only (the position-scalar step sets `length` itself)")
+        self.pos_dev.add_(1)
+        self.length += 1
+
+    def note_replay(self) -> None:
+        """A captured step was replayed: the graph advanced `pos_dev`, the host length follows."""
+        if self.length + 1 > self.max_len:
+            raise ValueError("StaticKVCache: %d + 1 positions exceed max_len=%d" % (self.length, self.max_len))
+        self.length += 1
+
+    def _own_rows(self) -> torch.Tensor:
+        return torch.arange(self.rows, dtype=torch.int32, device=self.device).view(-1, 1).repeat(1, self.max_len)
+
     def reorder(self, beam_idx: torch.Tensor) -> None:
-        """Beam search: sequence n continues what was sequence beam_idx[n].  Only the table moves (rows x length x 4 bytes)."""
+        """Beam search: sequence n continues what was sequence beam_idx[n].  Only the table moves (rows x length x 4 bytes), in place."""
         if self.src is None:
-            self.src = torch.arange(self.rows, dtype=torch.int32, device=self.device).view(-1, 1).repeat(1, self.max_len)
+            if self.replay:
+                raise ValueError("StaticKVCache.reorder: replay mode was enabled without beams (the table cannot appear after capture)")
+            self.src = self._own_rows()
         L = self.length
         if L:
             self.src[:, :L] = self.src[:, :L].index_select(0, beam_idx.to(self.device))
@@ -130,7 +184,19 @@ class StaticKVCache:
     def attend(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
         """One cached step of `layer` at position `length` (which the caller advances once per forward, after the last layer):
         q [N,H,d], k_new / v_new [N,H_kv,d] views of the projection output; cos / sin fp32 [d] rows of that position or None;
-        key_valid uint8 / bool [N, length+1] or None; slopes fp32 [H] or None.  Returns o [N, H*d] in q's dtype."""
+        key_valid uint8 / bool [N, length+1] or None; slopes fp32 [H] or None.  Returns o [N, H*d] in q's dtype.
+        Replay mode: the position is `pos_dev`, cos / sin are the whole fp32 tables [>= max_len, d] (or None) and the mask is the cache's
+        own `valid` (key_valid must be None)."""
+        if self.replay:
+            if key_valid is not None:
+                raise ValueError("StaticKVCache.attend: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
+            if self.uses_kernel(q, k_new.shape[1]):
+                from . import ops
+
+                return ops.decode_attn_cached_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.pos_dev, scale, cos_table=cos,
+                                                  sin_table=sin, src=self.src, key_valid=self.valid, slopes=slopes)
+            self.kernel_steps = False   # (the restatement reads the position back to the host: such a step cannot be captured)
+            return self.attend_reference(layer, q, k_new, v_new, scale, cos=cos, sin=sin, slopes=slopes)
         if self.uses_kernel(q, k_new.shape[1]):
             from . import ops
 
@@ -141,8 +207,19 @@ class StaticKVCache:
     def attend_reference(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
         """What csrc/decode_cache.hip does, in plain torch on any device and dtype: rotary (fp32 at least, k rounded to the cache dtype once),
         append at slot `length` of the row's own row, gather keys 0..length through the table, ALiBi slope * (j - length), padding mask,
-        softmax in fp32 at least, a fully masked row -> 0."""
+        softmax in fp32 at least, a fully masked row -> 0.  Replay mode: the position is read from `pos_dev` (not from `length`), cos / sin
+        are the whole tables, of which row `pos` is taken, and the mask is columns 0..pos of `valid`."""
         pos, N, H, d = self.length, q.shape[0], q.shape[1], q.shape[2]
+        if self.replay:
+            pos = int(self.pos_dev.item())
+            if key_valid is not None:
+                raise ValueError("StaticKVCache.attend_reference: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
+            key_valid = self.valid
+            if cos is not None:
+                if cos.dim() != 2 or cos.shape[0] < self.max_len:
+                    raise ValueError("StaticKVCache: replay mode takes the whole cos / sin tables [>= max_len, d]")
+                if 0 <= pos < cos.shape[0]:
+                    cos, sin = cos[pos], sin[pos]
         if pos < 1 or pos >= self.max_len:
             raise ValueError("StaticKVCache: a cached step needs 1 <= length < max_len (length=%d, max_len=%d)" % (pos, self.max_len))
         ct = torch.float64 if q.dtype == torch.float64 else torch.float32

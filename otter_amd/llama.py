@@ -186,7 +186,10 @@ class LlamaAttention(nn.Module):
                 q, k, v = qkv[:, :H * d], qkv[:, H * d:(H + Hk) * d], qkv[:, (H + Hk) * d:]
             else:
                 q, k, v = self.q_proj(x)[:, 0], self.k_proj(x)[:, 0], self.v_proj(x)[:, 0]
-            c, s_ = (cos[:, 0], sin[:, 0]) if cos.dim() == 3 else (cos[0], sin[0])
+            if cache.replay:                                                    # the whole tables: the kernel takes row pos itself
+                c, s_ = cos, sin
+            else:
+                c, s_ = (cos[:, 0], sin[:, 0]) if cos.dim() == 3 else (cos[0], sin[0])
             o = cache.attend(layer, q.view(B, H, d), k.view(B, Hk, d), v.view(B, Hk, d), self.scale, cos=c, sin=s_, key_valid=key_valid)
             return self.o_proj(o.view(B, 1, H * d)), None
         if flash:
@@ -305,6 +308,22 @@ class LlamaModel(LlamaPreTrainedModel):
                 cache.fill(i, k, v)                          # legacy layout: k, v [B,H,S,d]
             cache.length = S
             return BaseModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=cache)
+        if cache.replay:
+            # replay mode (kv_cache.py): the position, the mask and the beam table are the cache's own device buffers and the kernel takes
+            # its rotary row from the whole table (built to the cache's capacity on the first such step, before any capture) -- nothing
+            # below depends on the position, so this branch can be captured once and replayed (generate(..., graph_decode=True))
+            if position_ids is not None:
+                raise ValueError("LlamaModel: custom position_ids cannot follow a StaticKVCache in replay mode (the position is the cache's own)")
+            cos_t, sin_t = self.rotary_emb.tables(cache.max_len, x.device)
+            delta = None
+            for i, layer in enumerate(self.layers):
+                if delta is not None and getattr(layer, "gated_cross_attn_layer", None) is not None:
+                    x = x + delta
+                    delta = None
+                x, _, delta = layer(x, cos=cos_t, sin=sin_t, key_valid=None, deferred=delta, defer_out=True, static=(cache, i))
+            _, x = self.norm(x, delta=delta, out_dtype=OF.compute_dtype_for(x))
+            cache.advance()
+            return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
         pos = cache.length
         cos_t, sin_t = self.rotary_emb.tables(pos + 1, x.device)
         if position_ids is None:

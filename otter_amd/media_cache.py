@@ -43,6 +43,7 @@ class MediaCache:
         self.T_img = self.n = self.heads = 0
         self.mask_mode = MASK_EQ
         self.filled = False
+        self.fixed_address = False      # generate(..., graph_decode=True): `seen` is read by a captured graph and must never be replaced
 
     # ---- bookkeeping ----------------------------------------------------------------------------------------------------------------
 
@@ -108,7 +109,9 @@ class MediaCache:
 
     def reorder(self, beam_idx: torch.Tensor) -> None:
         """Beam search: row n continues what was row beam_idx[n] (a row of the same sentence).  Only the counts move."""
-        if self.filled:
+        if self.filled and self.fixed_address:
+            self.seen.copy_(self.seen.index_select(0, beam_idx.to(self.seen.device)))
+        elif self.filled:
             self.seen = self.seen.index_select(0, beam_idx.to(self.seen.device))
 
     # ---- the cached step ------------------------------------------------------------------------------------------------------------

@@ -640,8 +640,13 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         None or "dynamic" is the growing tuple cache.  `cross_attention_cache=True` (needs a cached mode) makes every cached step return
         what the last position of the full re-forward returns: a MediaCache (otter_amd/media_cache.py) carries each row's <image> count and
         the projected media, so the step attends to the image instead of reproducing the reference's zero; without it every path is
-        unchanged."""
+        unchanged.  `graph_decode=True` (needs cache_implementation="static" AND cross_attention_cache=True) captures one cached step
+        into a graph after a short warm-up and replays it for every further step (otter_amd/graph_decode.py); the tokens are those of
+        the same call without it.  Both are needed because a captured step must be one chain of launches at fixed addresses: only the
+        static cache keeps keys and values in place, and the legacy cached gated block forks a side stream and re-projects the media
+        every step -- a graph of it would have parallel branches -- while the MediaCache step is a single chain."""
         from .generation import generate_tokens, resolve_max_length
+        from .graph_decode import GraphDecodeStep
         from .kv_cache import StaticKVCache, cache_geometry
         from .media_cache import MediaCache
 
@@ -653,10 +658,15 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         static = cache_impl == "static"
         use_cache = use_cache or static
         media = [None]                                       # the MediaCache of this call, created beside the KV cache
-        if bool(generate_kwargs.pop("cross_attention_cache", False)):
+        want_media = bool(generate_kwargs.pop("cross_attention_cache", False))
+        graph_decode = bool(generate_kwargs.pop("graph_decode", False))
+        if graph_decode and not (static and want_media):
+            raise ValueError("generate: graph_decode=True needs cache_implementation='static' and cross_attention_cache=True")
+        if want_media:
             if not use_cache:
                 raise ValueError("generate: cross_attention_cache=True needs use_cache=True or cache_implementation='static'")
             media[0] = False                                 # (wanted, not created yet)
+        graph_step = [None]                                  # the GraphDecodeStep of this call, created after the prompt pass
         generate_kwargs.setdefault("eos_token_id", self.eoc_token_id)
         self._encode_vision_x(vision_x=vision_x)
         if num_beams > 1:   # perceiver output repeated per beam: same conditioning as encoding the repeated frames, 1/num_beams the work
@@ -689,6 +699,11 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
                     if beam_idx is not None:
                         past.reorder(beam_idx)               # the table moves, the cache does not
                     return_ids = ids[:, -1:]
+                if graph_decode and past.length > 0:         # every cached step: replay mode, one graph replay after the warm-up
+                    if graph_step[0] is None:
+                        past.enable_replay(mask[:, :past.length] if mask is not None else None, beams=num_beams > 1)
+                        graph_step[0] = GraphDecodeStep(lm, past, media[0])
+                    return graph_step[0](return_ids), past
                 out = lm(input_ids=return_ids, attention_mask=mask, past_key_values=past, use_cache=True, **mkw)
                 return out.logits[:, -1, :], past
             if use_cache and past is not None:
@@ -702,6 +717,8 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         try:
             return generate_tokens(step, lang_x, attention_mask, **generate_kwargs)
         finally:
+            if graph_step[0] is not None:
+                graph_step[0].release()
             self.lang_encoder.clear_conditioned_layers()
 
 

@@ -465,6 +465,22 @@ class MPTModel(MPTPreTrainedModel):
             cache.length = S
             return BaseModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=cache)
         x = self.wte(input_ids)
+        if cache.replay:
+            # replay mode (kv_cache.py): the position, the mask and the table are the cache's own device buffers -- nothing below depends
+            # on the position, so this branch can be captured once and replayed (generate(..., graph_decode=True))
+            if self._slopes is None or self._slopes.device != x.device:
+                self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
+            slopes = self._slopes.float().contiguous()
+            delta = None
+            for i, block in enumerate(self.blocks):
+                if delta is not None and getattr(block, "gated_cross_attn_layer", None) is not None and not _gated_takes_deferred(block, x, delta):
+                    x = x + delta
+                    delta = None
+                out = block(x, deferred=delta, defer_out=True, static=(cache, i, slopes, None))
+                x, delta = out[0], out[3]
+            _, x = self.norm_f.add_forward(x, delta)
+            cache.advance()
+            return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
         pos = cache.length
         if self._slopes is None or self._slopes.device != x.device:
             self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)

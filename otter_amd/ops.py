@@ -32,6 +32,12 @@ class _Workspace:
             self.bufs[key] = b
         return b
 
+    def drop_stream(self, device, stream) -> None:
+        """Forget the buffer of one stream.  otter_amd/graph_decode.py calls it at the end of every generate(graph_decode=True) call for
+        its capture stream (one per device, kept for the life of the process): the buffer is allocated again, in ordinary memory, by the
+        next call's warm-up steps, so nothing of this project's that is keyed by that stream outlives a call."""
+        self.bufs.pop((device.type, device.index, stream.cuda_stream), None)
+
 
 _ws = _Workspace()
 
@@ -594,6 +600,66 @@ def decode_attn_cached(q, k_new, v_new, k_cache, v_cache, pos, scale, cos=None, 
         v_cache.stride(0), v_cache.stride(1), K.ptr(src), src.stride(0) if src is not None else 0, K.ptr(key_valid),
         key_valid.stride(0) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 128,
         float(scale), K.stream()), "decode_attn_cached")
+    return o
+
+
+def decode_attn_cached_dyn_workspace_bytes(N: int, H: int, S_max: int) -> int:
+    """OTTER_DECODE_CACHED_DYN_WORKSPACE_BYTES of include/otter_hip.h."""
+    return N * H * ((S_max + 127) // 128) * 130 * 4
+
+
+def decode_attn_cached_dyn(q, k_new, v_new, k_cache, v_cache, pos_dev, scale, cos_table=None, sin_table=None, src=None, key_valid=None, slopes=None,
+                           out=None):
+    """decode_attn_cached with the position in device memory (otter_decode_attn_cached_dyn): pos_dev int32 [1] on the device, read by the
+    kernel (a value outside [1, S_max) makes the call a no-op); cos_table / sin_table fp32 [>= S_max, 128] (the kernel takes row pos) or
+    None; src int32 [N, >= S_max - 1]; key_valid uint8 [N, >= S_max].  No argument of the launch depends on the position: the same call,
+    captured in a graph, serves every step.  Everything else as decode_attn_cached.  Returns o [N,H*128] bf16 (`out`: a contiguous bf16
+    [N,H*128] tensor to write instead)."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, pos_dev, cos_table, sin_table, src, key_valid, slopes, out)
+    if q.dim() != 3:
+        raise K.OtterHipError("decode_attn_cached_dyn: q must be [N,H,128]")
+    N, H = q.shape[:2]
+    if not (_decode_new_ok(q, N, H) and _decode_new_ok(k_new, N, H) and _decode_new_ok(v_new, N, H)):
+        raise K.OtterHipError("decode_attn_cached_dyn: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
+    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
+    for t in (k_cache, v_cache):
+        if (t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 128) or t.stride(3) != 1 or t.stride(2) != 128
+                or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < S_max * 128 or t.data_ptr() % 16):
+            raise K.OtterHipError("decode_attn_cached_dyn: k_cache / v_cache must be bf16 [N,H,S_max,128] with key stride 128, unit dim stride, 16-B aligned")
+    if S_max < 2 or S_max > DECODE_CACHED_MAX_KEYS:
+        raise K.OtterHipError(f"decode_attn_cached_dyn: S_max={S_max} outside [2, {DECODE_CACHED_MAX_KEYS}]")
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
+        raise K.OtterHipError("decode_attn_cached_dyn: pos_dev must be an int32 tensor of one element")
+    if (cos_table is None) != (sin_table is None):
+        raise K.OtterHipError("decode_attn_cached_dyn: cos_table and sin_table must both be given or both be None")
+    tab_stride = 0
+    if cos_table is not None:
+        for t in (cos_table, sin_table):
+            if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != 128 or t.stride(1) != 1 or t.stride(0) < 128
+                    or t.stride() != cos_table.stride()):
+                raise K.OtterHipError("decode_attn_cached_dyn: cos_table / sin_table must be fp32 [>= S_max, 128] with a unit dim stride and equal strides")
+        tab_stride = cos_table.stride(0)
+    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < S_max - 1 or src.stride(1) != 1
+                            or (N > 1 and src.stride(0) < S_max - 1)):
+        raise K.OtterHipError("decode_attn_cached_dyn: src must be int32 [N, >= S_max - 1] with a unit column stride")
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < S_max
+                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < S_max)):
+        raise K.OtterHipError("decode_attn_cached_dyn: key_valid must be uint8 [N, >= S_max] with a unit column stride")
+    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
+        raise K.OtterHipError("decode_attn_cached_dyn: slopes must be contiguous fp32 [H]")
+    if out is None:
+        o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * 128) or not out.is_contiguous():
+        raise K.OtterHipError("decode_attn_cached_dyn: out must be a contiguous bf16 [N, H*128] tensor")
+    else:
+        o = out
+    ws = _ws.get(decode_attn_cached_dyn_workspace_bytes(N, H, S_max), q.device)
+    K.check(K.lib().otter_decode_attn_cached_dyn(
+        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
+        v_new.stride(1), K.ptr(cos_table), K.ptr(sin_table), tab_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1),
+        v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), K.ptr(src), max(src.stride(0), S_max - 1) if src is not None else 0,
+        K.ptr(key_valid), max(key_valid.stride(0), S_max) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(),
+        N, H, pos_dev.data_ptr(), S_max, 128, float(scale), K.stream()), "decode_attn_cached_dyn")
     return o
 
 
