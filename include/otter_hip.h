@@ -448,12 +448,22 @@ int otter_xattn_decode(const void* q, int64_t q_stride, const void* k, const voi
  *       multiplies the finished fp32 sum, then bias, then activation.  N >= 1, K % 16 == 0, ldw % 16 == 0, ldx % 8 == 0; x, qweight,
  *       y 16-byte aligned.  workspace: at least OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K) bytes (fp32 split-K partials, combined in
  *       a fixed order: two calls on the same inputs give the same bits).
+ *   otter_gemm_w8_rows   the same product, arguments and rules for 1 <= M <= 64: the linears of a one-token step of 17 to 64 rows
+ *       (batch x beams).  The weight is still streamed once; x is shared by a workgroup through LDS.  workspace: at least
+ *       OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES(M, N, K) bytes.  The K split and with it the summation order of every output element
+ *       depend on (N, K) only: two calls give the same bits, and row m of y has the same bits whatever M is and whatever the other
+ *       rows of x hold.  For M <= 16 the result equals otter_gemv_w8's to rounding, NOT bit for bit (the two sum K in different
+ *       groupings).
  *   otter_dequant_w8   out[n, k] = bf16(float(q[n, k]) * scale[n]), out bf16 [N, K] with row stride ldo (ldo % 8 == 0, 16-byte
- *       aligned): the pass in front of the library GEMM when more than 16 rows arrive (prompt prefill).
+ *       aligned): the pass in front of the library GEMM for prompt passes of more than 16 rows (and one-token steps of more than 64).
  * ------------------------------------------------------------------------------------------------------- */
 #define OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K) ((int64_t)8 * (int64_t)(M) * (int64_t)(N) * 4)   /* at most 8 K ranges, whatever K */
 int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype, void* y,
                   int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes, void* stream);
+#define OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES(M, N, K) ((int64_t)8 * (int64_t)(M) * (int64_t)(N) * 4)   /* at most 8 K ranges, whatever K */
+int otter_gemm_w8_rows(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype,
+                       void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes,
+                       void* stream);
 int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------

@@ -140,6 +140,7 @@ SIGNATURES = {
                                             _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _vp]),
     "otter_xattn_decode": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _vp]),
     "otter_gemv_w8": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
+    "otter_gemm_w8_rows": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
     "otter_dequant_w8": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp]),
     "otter_qk_norm_rope_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _i64, _vp]),
     "otter_qk_norm_rope_bwd_blocks": (_i64, [_i64, _i64]),

@@ -6,7 +6,8 @@
 //                 B x num_beams rows through every decoder linear, so the product is a single pass over the weight.  x is NOT quantised
 //                 and the i8 matrix instruction is not used: q is converted to bf16 in registers (exact for |q| <= 127) and fed to
 //                 v_mfma_f32_16x16x32_bf16 with x padded to 16 rows; fp32 accumulation, the scale applied to the fp32 sum.
-// otter_dequant_w8  out[n, k] = bf16(float(q[n, k]) * scale[n]): the streaming pass behind the more-than-16-row (prefill) path.
+// otter_gemm_w8_rows  the same product for 1 <= M <= 64: one-token steps of 17 to 64 rows (B x num_beams) still stream the weight once.
+// otter_dequant_w8  out[n, k] = bf16(float(q[n, k]) * scale[n]): the streaming pass behind the prompt (prefill) path.
 //
 // GEMV decomposition.  A workgroup of 4 waves owns 16 R output rows (R = 1, or 2 from N = 16384 up) and one of S contiguous K ranges; its
 // waves cut that range in four (split-K inside the workgroup, combined through LDS in wave order).  Per 64-wide K step a lane loads 16
@@ -16,6 +17,19 @@
 // see the same permutation of K inside a step, which a dot product does not notice.  Steps are issued four at a time, the next four
 // requested before the current four are consumed.  With S > 1 (few rows, long K: out_proj, down_proj) every workgroup writes its raw
 // fp32 sums to the workspace and a second kernel adds the S ranges in order: no floating-point atomics, bit-identical from call to call.
+//
+// Rows decomposition (gemm_w8_rows).  At 64 rows x is 4 times the GEMV's and fragment-shaped loads of it by every wave would dominate the
+// load path, so here the four waves of a workgroup take four DIFFERENT 16-row weight tiles (64 output columns per workgroup) over the SAME
+// K range and share x through LDS.  K advances in chunks of 256 (four 64-wide steps).  Per chunk a wave loads its 4 x 16 weight bytes per
+// lane straight into VGPRs exactly as the GEMV does; the workgroup loads the chunk of x, rows 0 .. 16 ceil(M / 16) - 1 (rows >= M are
+// zero-filled, not read), as full 512-byte row pieces and writes them to one of two LDS images [64 rows][32 slots of 16 B], slot c of row r
+// stored at c ^ (r & 15): the 16 rows that one lane group of a 16-byte LDS read covers then fall on 16 different slots of the 256-byte
+// bank row.  One barrier per chunk: the loads of chunk c + 1 (weights to registers, x to registers) are issued before chunk c is
+// consumed and x is written to the other image after it.  Each converted weight fragment (cvt8, once per weight element) feeds the MFMAs
+// of all ceil(M / 16) column blocks.  Split-K as above, but ACROSS workgroups only: the split count S depends on (N, K) alone, every
+// output element is one MFMA chain per K range in ascending K and the S ranges are added in order, so row m of y has the same bits
+// whatever M is and whatever the other rows hold.  (A wave here sums a whole range where the GEMV's four waves sum quarters of it: for
+// M <= 16 the two kernels agree to rounding, not bit for bit.)
 #include "common.h"
 
 typedef __bf16 w8_bf16x8_t __attribute__((ext_vector_type(8)));
@@ -163,6 +177,115 @@ __global__ __launch_bounds__(NT) void gemv_w8_reduce_kernel(W8Args a) {
     st_from_f32(a.y, m * a.ldy + n, a.y_dtype, w8_epilogue(v, n, a));
 }
 
+// ---- rows kernel (17 to 64 rows; any 1 <= M <= 64 is accepted) -----------------------------------------------------------------------------
+
+constexpr int ROWS_MAX_M = 64;
+constexpr int ROWS_BN = 16 * WAVES;                 // output columns (weight rows) per workgroup
+constexpr int ROWS_KC = UNROLL * KSTEP;             // K elements per chunk
+constexpr int ROWS_SLOTS = ROWS_KC / 8;             // 16-byte slots per x row of a chunk (32: two 256-byte bank rows)
+constexpr int ROWS_MAX_SPLIT = 8;                   // OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES of the header is sized for it
+constexpr int64_t ROWS_WG_TARGET = 256;             // K is split further only while there is at most one workgroup per CU of a 256-CU part
+constexpr int64_t ROWS_MIN_K_PER_WG = 512;
+
+template <int MB>
+__global__ __launch_bounds__(NT) void gemm_w8_rows_kernel(W8Args a) {          // a.T: chunks in all, a.q: chunks per K range
+    __shared__ uint4 xs[2][ROWS_MAX_M * ROWS_SLOTS];                           // 2 x 32 KB
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    const int64_t n0 = (int64_t)blockIdx.x * ROWS_BN + 16 * wv;
+    const int s = blockIdx.y;
+    const int c0 = s * a.q, c1 = min(c0 + a.q, a.T);
+
+    const bool row_ok = n0 + r16 < a.N;
+    const int8_t* wp = a.w + (row_ok ? n0 + r16 : 0) * a.ldw + 16 * g;
+
+    auto load_w = [&](uint4 (&w)[UNROLL], int c) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int64_t k = (int64_t)c * ROWS_KC + u * KSTEP;
+            const bool ok = row_ok && k + 16 * g < a.K;                        // K % 16 == 0: a lane's 16 elements are all inside or all outside
+            w[u] = ok ? *reinterpret_cast<const uint4*>(wp + k) : make_uint4(0, 0, 0, 0);
+        }
+    };
+    // x chunk: 16 MB rows x 32 slots, 2 MB slots per thread; 32 consecutive threads read one 512-byte row piece
+    auto load_x = [&](uint4 (&xr)[2 * MB], int c) {
+#pragma unroll
+        for (int j = 0; j < 2 * MB; ++j) {
+            const int idx = j * NT + tid, row = idx / ROWS_SLOTS, cc = idx % ROWS_SLOTS;
+            const int64_t k = (int64_t)c * ROWS_KC + 8 * cc;
+            const bool ok = row < a.M && k < a.K;                              // (K % 8 == 0: the 8 elements are all inside or all outside)
+            xr[j] = ok ? *reinterpret_cast<const uint4*>(a.x + (int64_t)row * a.ldx + k) : make_uint4(0, 0, 0, 0);
+        }
+    };
+    auto store_x = [&](int buf, const uint4 (&xr)[2 * MB]) {
+#pragma unroll
+        for (int j = 0; j < 2 * MB; ++j) {
+            const int idx = j * NT + tid, row = idx / ROWS_SLOTS, cc = idx % ROWS_SLOTS;
+            xs[buf][row * ROWS_SLOTS + (cc ^ (row & 15))] = xr[j];
+        }
+    };
+
+    // a tile is [weight row, x row] as in the GEMV: acc[mb][i] of a lane = weight row 4 (lane >> 4) + i of the wave's 16, x row 16 mb + (lane & 15)
+    w8_f32x4_t acc[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) acc[mb] = w8_f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    auto consume = [&](const uint4 (&w)[UNROLL], int buf) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const w8_bf16x8_t wa = cvt8(w[u].x, w[u].y), wb = cvt8(w[u].z, w[u].w);
+            const int cc = 8 * u + 2 * g;
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb) {
+                const uint4* xrow = &xs[buf][(16 * mb + r16) * ROWS_SLOTS];
+                const uint4 xa = xrow[cc ^ r16], xb = xrow[(cc + 1) ^ r16];
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(w8_bf16x8_t, xa), acc[mb], 0, 0, 0);
+                acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb, __builtin_bit_cast(w8_bf16x8_t, xb), acc[mb], 0, 0, 0);
+            }
+        }
+    };
+
+    uint4 wc[UNROLL], wn[UNROLL], xr[2 * MB];
+    if (c0 < c1) {
+        load_w(wc, c0);
+        load_x(xr, c0);
+        store_x(0, xr);
+    }
+    __syncthreads();
+    for (int c = c0; c < c1; c += 2) {                                          // ping-pong between the two register batches / LDS images
+        const bool more = c + 1 < c1;                                           // (all conditions uniform over the workgroup)
+        if (more) {
+            load_w(wn, c + 1);
+            load_x(xr, c + 1);
+        }
+        consume(wc, 0);
+        if (more) store_x(1, xr);
+        __syncthreads();
+        if (more) {
+            const bool more2 = c + 2 < c1;
+            if (more2) {
+                load_w(wc, c + 2);
+                load_x(xr, c + 2);
+            }
+            consume(wn, 1);
+            if (more2) store_x(0, xr);
+            __syncthreads();
+        }
+    }
+
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        const int m = 16 * mb + r16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t n = n0 + 4 * g + i;
+            if (m >= a.M || n >= a.N) continue;
+            if (a.S == 1) st_from_f32(a.y, (int64_t)m * a.ldy + n, a.y_dtype, w8_epilogue(acc[mb][i], n, a));
+            else a.part[((int64_t)s * a.M + m) * a.N + n] = acc[mb][i];
+        }
+    }
+}
+
 // one workgroup per weight row, 16 elements per thread and trip
 __global__ __launch_bounds__(NT) void dequant_w8_kernel(const int8_t* __restrict__ q, int64_t ldw, const float* __restrict__ scale,
                                                         bf16_t* __restrict__ out, int64_t ldo, int K) {
@@ -229,6 +352,53 @@ int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, 
     if (S > 1) {
         hipLaunchKernelGGL(gemv_w8_reduce_kernel, dim3((unsigned)cdiv64(M * N, NT)), dim3(NT), 0, st, a);
         OTTER_CHECK_LAUNCH("gemv_w8 (reduce)");
+    }
+    return OTTER_OK;
+}
+
+int otter_gemm_w8_rows(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype,
+                       void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+    OTTER_REQUIRE(x && qweight && scale && y && workspace, "gemm_w8_rows: null pointer");
+    OTTER_REQUIRE(M >= 1 && M <= ROWS_MAX_M, "gemm_w8_rows: M=%d outside [1, 64]", (int)M);
+    OTTER_REQUIRE(N >= 1 && N <= (int64_t)1 << 30, "gemm_w8_rows: N=%ld outside [1, 2^30]", (long)N);
+    OTTER_REQUIRE(K >= 16 && K % 16 == 0 && K <= (int64_t)1 << 30, "gemm_w8_rows: K=%d must be a positive multiple of 16", (int)K);
+    OTTER_REQUIRE(ldw % 16 == 0 && ldx % 8 == 0 && (((uintptr_t)x | (uintptr_t)qweight | (uintptr_t)y) & 15) == 0,
+                  "gemm_w8_rows: alignment (x, qweight, y 16-byte aligned; ldw %% 16 == 0; ldx %% 8 == 0)");
+    OTTER_REQUIRE(ldw >= K && ldx >= K && ldy >= N, "gemm_w8_rows: a leading dimension is smaller than the row it holds");
+    OTTER_REQUIRE((y_dtype == OTTER_F32 || y_dtype == OTTER_BF16) && (!bias || bias_dtype == OTTER_F32 || bias_dtype == OTTER_BF16),
+                  "gemm_w8_rows: y / bias dtype must be OTTER_F32 or OTTER_BF16");
+    OTTER_REQUIRE(act == 0 || act == 1, "gemm_w8_rows: act=%d (0 none, 1 GELU)", act);
+    const int64_t need = OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES(M, N, K);
+    OTTER_REQUIRE(workspace_bytes >= need, "gemm_w8_rows: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+
+    // the split is a function of (N, K) only -- never of M -- so that a row's summation order does not depend on what it is batched with
+    const int64_t base = cdiv64(N, ROWS_BN);
+    int S = 1;
+    while (base * S <= ROWS_WG_TARGET && S < ROWS_MAX_SPLIT && K / (2 * S) >= ROWS_MIN_K_PER_WG) S *= 2;
+    OTTER_REQUIRE(base <= 0x7fffffff, "gemm_w8_rows: internal grid");
+
+    W8Args a;
+    a.x = (const bf16_t*)x; a.ldx = ldx;
+    a.w = (const int8_t*)qweight; a.ldw = ldw;
+    a.scale = scale; a.bias = bias; a.bias_dtype = bias_dtype;
+    a.y = y; a.ldy = ldy; a.y_dtype = y_dtype;
+    a.part = (float*)workspace;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.act = act; a.S = S;
+    a.T = (int)cdiv64(K, ROWS_KC);
+    a.q = (int)cdiv64(a.T, S);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)base, (unsigned)S);
+    switch ((int)cdiv64(M, 16)) {
+        case 1: hipLaunchKernelGGL(gemm_w8_rows_kernel<1>, grid, dim3(NT), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(gemm_w8_rows_kernel<2>, grid, dim3(NT), 0, st, a); break;
+        case 3: hipLaunchKernelGGL(gemm_w8_rows_kernel<3>, grid, dim3(NT), 0, st, a); break;
+        default: hipLaunchKernelGGL(gemm_w8_rows_kernel<4>, grid, dim3(NT), 0, st, a); break;
+    }
+    OTTER_CHECK_LAUNCH("gemm_w8_rows");
+    if (S > 1) {
+        hipLaunchKernelGGL(gemv_w8_reduce_kernel, dim3((unsigned)cdiv64(M * N, NT)), dim3(NT), 0, st, a);
+        OTTER_CHECK_LAUNCH("gemm_w8_rows (reduce)");
     }
     return OTTER_OK;
 }

@@ -745,6 +745,39 @@ def gemv_w8(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfloat16
     return y
 
 
+GEMM_W8_ROWS_MAX_ROWS = 64            # include/otter_hip.h: 1 <= M <= 64
+
+
+def gemm_w8_rows_workspace_bytes(M: int, N: int, K: int) -> int:
+    """OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES of include/otter_hip.h."""
+    return 8 * M * N * 4
+
+
+def gemm_w8_rows(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfloat16, out=None):
+    """gemv_w8's product, arguments and rules for 1 <= M <= 64 (otter_gemm_w8_rows, csrc/w8.hip): the one-token steps of 17 to 64 rows.
+    Row m of the result has the same bits whatever M is and whatever the other rows of x hold."""
+    K.require_cuda(x, qweight, scale, bias, out)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise K.OtterHipError("gemm_w8_rows: x must be bf16 [M, K] with a unit column stride")
+    if not _w8_weight_ok(qweight, scale):
+        raise K.OtterHipError("gemm_w8_rows: qweight int8 [N, K] (K % 16 == 0, row stride % 16 == 0, 16-B aligned), scale contiguous fp32 [N]")
+    M, Kd = x.shape
+    N = qweight.shape[0]
+    if Kd != qweight.shape[1] or not 1 <= M <= GEMM_W8_ROWS_MAX_ROWS:
+        raise K.OtterHipError(f"gemm_w8_rows: x {tuple(x.shape)} against qweight {tuple(qweight.shape)} (1 <= M <= {GEMM_W8_ROWS_MAX_ROWS})")
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        raise K.OtterHipError("gemm_w8_rows: bias must be contiguous [N]")
+    y = torch.empty((M, N), dtype=out_dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.device != x.device:
+        raise K.OtterHipError("gemm_w8_rows: out must be [M, N] with a unit column stride on x's device")
+    ldx, ldy = (x.stride(0), y.stride(0)) if M > 1 else (Kd, N)      # (the row stride of a one-row view is arbitrary)
+    ws = _ws.get(gemm_w8_rows_workspace_bytes(M, N, Kd), x.device)
+    K.check(K.lib().otter_gemm_w8_rows(x.data_ptr(), ldx, qweight.data_ptr(), qweight.stride(0), scale.data_ptr(), K.ptr(bias),
+                                       K.dt(bias) if bias is not None else K.F32, y.data_ptr(), ldy, K.dt(y), M, N, Kd, int(act),
+                                       ws.data_ptr(), ws.numel(), K.stream()), "gemm_w8_rows")
+    return y
+
+
 def dequant_w8(qweight, scale, out=None):
     """out [N, K] bf16 = bf16(float(qweight) * scale[:, None]) (otter_dequant_w8, csrc/w8.hip); `out`: a caller-owned bf16 [N, K] view with
     unit column stride and a row stride that is a multiple of 8."""

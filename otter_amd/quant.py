@@ -1,6 +1,6 @@
 """Int8 weight-only form of the frozen decoder for generation.
 
-`generate(use_cache=True)` feeds the frozen decoder one token per sequence: every decoder linear sees B x num_beams rows (1 to 16) and
+`generate(use_cache=True)` feeds the frozen decoder one token per sequence: every decoder linear sees B x num_beams rows (1 to 64) and
 the step is a single pass over the weights.  Storing those weights as int8 with one fp32 scale per output row halves the bytes a step
 moves and the decoder's footprint; the activations stay bf16 and the accumulation fp32 (csrc/w8.hip).  This is an opt-in, in-memory
 transformation applied after loading (`OtterForConditionalGeneration.quantize_decoder_int8()`); nothing on the training path changes.
@@ -14,6 +14,7 @@ same bits on the GPU and on the CPU.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -24,6 +25,21 @@ from . import functional as OF
 from . import ops
 
 GEMV_MAX_ROWS = ops.GEMV_W8_MAX_ROWS
+ROWS_MAX_ROWS = ops.GEMM_W8_ROWS_MAX_ROWS
+
+
+def route(rows: int, one_token: bool) -> str:
+    """Which product an Int8FrozenLinear runs for a GPU input of `rows` rows (leading dimensions flattened):
+      "gemv"     rows <= 16: ops.gemv_w8;
+      "rows"     17 <= rows <= 64 in a one-token step (the input has at least three dimensions and x.shape[-2] == 1, as every cached
+                 step of the MPT and LLaMA hosts passes it): ops.gemm_w8_rows.  OTTER_W8_ROWS=0 sends this case to "dequant" (A/B);
+      "dequant"  everything else -- prompt passes of any size above 16 rows, steps of more than 64 rows: ops.dequant_w8 + library GEMM.
+    """
+    if rows <= GEMV_MAX_ROWS:
+        return "gemv"
+    if one_token and rows <= ROWS_MAX_ROWS and os.environ.get("OTTER_W8_ROWS", "1") != "0":
+        return "rows"
+    return "dequant"
 
 
 def quantize_weight_int8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -71,7 +87,9 @@ class Int8FrozenLinear(nn.Module):
     forward(x, act=None) -- `act="gelu"` applies the exact-erf GELU to the output:
       * GPU input of at most 16 rows (leading dimensions flattened): `ops.gemv_w8`, one pass over the int8 weight, scale / bias / GELU in
         its epilogue.  x is cast to bf16 if it is not; the output has the compute dtype the unquantised layer would have produced.
-      * GPU input of more than 16 rows (prompt prefill): `ops.dequant_w8` into the process-wide bf16 scratch, then the library GEMM.
+      * GPU input of 17 to 64 rows in a one-token step ([rows, 1, K]: batch x beams of a cached step): `ops.gemm_w8_rows`, the same
+        single pass over the int8 weight (see `route`).
+      * Any other GPU input (prompt prefill, more than 64 rows): `ops.dequant_w8` into the process-wide bf16 scratch, then the library GEMM.
       * CPU input: F.linear(x, dequantize_weight_int8(...), bias).  The ONE deliberate exception to this package's "no CPU fallback"
         rule: the host contract (module swap, parity with the fake-quantised model, error paths) has to be testable without a GPU.  No
         product path runs the decoder on the CPU.
@@ -121,10 +139,12 @@ class Int8FrozenLinear(nn.Module):
         lead = x.shape[:-1]
         x2 = x.reshape(-1, self.in_features)
         xb = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
-        if xb.shape[0] <= GEMV_MAX_ROWS:
+        how = route(xb.shape[0], x.dim() >= 3 and x.shape[-2] == 1)
+        if how != "dequant":
             if xb.stride(1) != 1 or (xb.shape[0] > 1 and xb.stride(0) % 8) or xb.data_ptr() % 16:
                 xb = xb.contiguous()
-            y = ops.gemv_w8(xb, self.qweight, self.scale, self.bias, 1 if act else 0, out_dtype=cd)
+            product = ops.gemv_w8 if how == "gemv" else ops.gemm_w8_rows
+            y = product(xb, self.qweight, self.scale, self.bias, 1 if act else 0, out_dtype=cd)
             return y.view(lead + (self.out_features,))
         n, k = self.qweight.shape
         w = ops.dequant_w8(self.qweight, self.scale, out=_dequant_scratch(n * k, x.device)[: n * k].view(n, k))
