@@ -422,6 +422,42 @@ int otter_decode_attn_cached_dyn(const void* q, int64_t q_row_stride, int64_t q_
                                  int64_t N, int64_t H, const int32_t* pos_dev, int64_t S_max, int64_t head_dim, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_decode_attn_cached_i8 / otter_decode_attn_cached_i8_dyn -- otter_decode_attn_cached / _dyn over an INT8 static cache
+ * (otter_amd/kv_cache.py, kv_dtype="int8"): a cached vector is 128 int8 codes and one fp32 scale.
+ *   k_cache / v_cache  int8 codes, indexed [row, h, key, 128]: row and head strides in elements (multiples of 16, head stride
+ *            >= S_max * 128), key stride 128, 16-byte aligned.
+ *   k_scale / v_scale  fp32, indexed [row, h, key]: row and head strides in elements (head stride >= S_max), key stride 1, 4-byte aligned.
+ * For x = the vector the bf16 cache would store (k after rotary, rounded once to bf16; v as given), read as fp32:
+ *   amax = max |x[i]|;  scale = amax / 127 (1 when amax == 0);  code = clamp(rint(x[i] / scale), -127, 127) (half to even);
+ *   what attention sees is (float)code * scale.
+ * The step quantises the new token, writes its 128 + 128 codes and two scales into slot [n, h, pos] of row n, and attends over keys
+ * 0..pos with key pos in its dequantised form: it returns what "append, then attend over the cache" returns.  Every other argument,
+ * the in-place invariant (no workgroup reads a slot or a scale this call writes), the fixed-order reductions, and the relation of the
+ * pair (at every pos in [1, S_max) the _dyn entry gives the bits of the scalar entry; outside it, it is a no-op) are as documented for
+ * otter_decode_attn_cached and otter_decode_attn_cached_dyn.
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES(N, H, Sk) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(Sk) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_i8(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                const float* cos_rows, const float* sin_rows, int64_t cos_row_stride, void* k_cache, int64_t k_cache_row_stride,
+                                int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride, int64_t v_cache_head_stride,
+                                float* k_scale, int64_t k_scale_row_stride, int64_t k_scale_head_stride, float* v_scale,
+                                int64_t v_scale_row_stride, int64_t v_scale_head_stride, const int32_t* src, int64_t src_row_stride,
+                                const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace,
+                                int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim, float scale,
+                                void* stream);
+#define OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES(N, H, S_max) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(S_max) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                    int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                    const float* cos_table, const float* sin_table, int64_t table_row_stride, void* k_cache,
+                                    int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                    int64_t v_cache_head_stride, float* k_scale, int64_t k_scale_row_stride, int64_t k_scale_head_stride,
+                                    float* v_scale, int64_t v_scale_row_stride, int64_t v_scale_head_stride, const int32_t* src,
+                                    int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes,
+                                    void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, const int32_t* pos_dev,
+                                    int64_t S_max, int64_t head_dim, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * otter_xattn_decode -- the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
  * head_dim 64: N rows (batch x beams) of ONE query each attend over the projected media of their sentence.
  *   q        bf16 [N, H * 64] with a row stride (elements, a multiple of 8, >= H * 64), 16-byte aligned.

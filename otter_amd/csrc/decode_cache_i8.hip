@@ -1,0 +1,426 @@
+// decode_cache_i8.hip -- decode_cache.hip's cached generate() step over an INT8 static key / value cache (otter_amd/kv_cache.py:
+// StaticKVCache(kv_dtype="int8")), head_dim 128.  A cached vector is 128 int8 codes and one fp32 scale; the step quantises the new token as it
+// appends it and dequantises in registers while it attends.  Everything else -- N rows at one position, the beam table `src`, key_valid,
+// ALiBi, optional rotary evaluated in fp64 and rounded once, the in-place append at slot `pos` of the row's OWN row, keys < pos read through
+// the table, fixed-order reductions, the scalar / device-position pair of entry points -- is decode_cache.hip's, and so is the invariant the
+// in-place update rests on: no workgroup reads a slot (codes or scale) that this launch writes.  Scales are per token, so an append never
+// rewrites the scale of an earlier position.
+//
+// THE FORMAT (kv_cache.py states it once): for the vector x[128] the bf16 cache would hold (k after rotary, rounded once to bf16; v as given),
+// read as fp32:   amax = max |x[i]|;  scale = amax / 127 (1 when amax == 0);  code = clamp(rint(x[i] / scale), -127, 127);  value = code * scale.
+// Plain `/` and rintf (round-half-even): IEEE-exact ops, the same codes and scales as torch computes.  No reciprocal.
+//
+// The new token is attended in its DEQUANTISED form (codes and scale from LDS), so a step returns what "append, then attend over the cache"
+// returns.
+//
+// Shape: grid (key range, head, row), 256 threads.  A cached vector is 128 bytes, so an 8-lane group owns one key at a time (lane l8: dims
+// 16 l8 .. 16 l8 + 15, one 16-byte load each of K and V codes; the key's two scales are one 4-byte load each, the same address in all 8 lanes),
+// 32 groups, two keys per group in flight = 64 keys per iteration: s = k_scale * sum q[i] code_k[i] by an 8-lane butterfly, online softmax per
+// group, acc += (p * v_scale) * code_v[i].  The 32 groups are combined through LDS in a fixed order; with more than one range each workgroup
+// writes (m, l, o[128]) to the workspace and a second kernel combines the ranges in range order.
+//
+// The split rule is decode_cache.hip's with this kernel's 64 keys per iteration (that file is left byte for byte as it was, so the few lines
+// of the rule are restated here rather than moved).
+#include "common.h"
+
+namespace {
+
+constexpr int HD = 128, NT = 256, LANES = 8, GROUPS = NT / LANES, UNROLL = 2, KEYS_PER_ITER = GROUPS * UNROLL, DPL = HD / LANES;
+constexpr int MIN_KEYS_PER_SPLIT = 128, PART = 2 + HD;   // workspace record per (row, head, range): m, l, o[128]
+constexpr int64_t S_MAX_LIMIT = 65536;
+
+struct DqArgs {
+    const bf16_t* q; int64_t q_rs, q_hs;                  // new token: q / k / v [n, h, 128], row / head strides (elements), dim stride 1
+    const bf16_t* kn; int64_t kn_rs, kn_hs;
+    const bf16_t* vn; int64_t vn_rs, vn_hs;
+    const float *cs, *sn; int64_t cs_rs;                  // rotary row(s) of position pos, fp32 [128]; row stride 0 = shared; null = no rotary
+    int8_t* kc; int64_t kc_rs, kc_hs;                     // codes [row, h, key, 128]: row / head strides, key stride 128
+    int8_t* vc; int64_t vc_rs, vc_hs;
+    float* ks; int64_t ks_rs, ks_hs;                      // scales [row, h, key]: row / head strides, key stride 1
+    float* vs; int64_t vs_rs, vs_hs;
+    const int32_t* src; int64_t src_rs;                   // [N, >= pos] or null (= the row's own)
+    const uint8_t* kvalid; int64_t kv_rs;                 // [N, >= pos + 1] or null
+    const float* slopes;                                  // [H] or null
+    bf16_t* o;                                            // [N, H * 128]
+    float* part;                                          // [N * H * part_stride, PART] (nsplit > 1), part_stride >= nsplit
+    int N, H, pos, nsplit, kps, part_stride;
+    float scale;
+};
+
+// THE SPLIT RULE of decode_cache.hip (both entry points, host and device): about two workgroups per CU over all (row, head, range), at least
+// MIN_KEYS_PER_SPLIT keys per range, a multiple of KEYS_PER_ITER keys each.  The range count is not monotone in Sk, so the dyn grid is sized by
+// dq_max_ranges, the bound, not by the count at the capacity.
+struct DqSplit { int kps, nsplit; };
+
+__host__ __device__ inline int64_t dq_want(int64_t NH, int cus) {
+    const int64_t want = (2 * (int64_t)cus + NH - 1) / NH;
+    return want > 0 ? want : 1;
+}
+
+__host__ __device__ inline DqSplit dq_split(int64_t Sk, int64_t NH, int cus) {
+    const int64_t want = dq_want(NH, cus);
+    int64_t kps = (Sk + want - 1) / want;
+    if (kps < MIN_KEYS_PER_SPLIT) kps = MIN_KEYS_PER_SPLIT;
+    kps = (kps + KEYS_PER_ITER - 1) / KEYS_PER_ITER * KEYS_PER_ITER;
+    DqSplit s;
+    s.kps = (int)kps;
+    s.nsplit = (int)((Sk + kps - 1) / kps);
+    return s;
+}
+
+__host__ __device__ inline int64_t dq_max_ranges(int64_t S_max, int64_t NH, int cus) {
+    const int64_t want = dq_want(NH, cus), by_keys = (S_max + MIN_KEYS_PER_SPLIT - 1) / MIN_KEYS_PER_SPLIT;
+    return want < by_keys ? want : by_keys;
+}
+
+__device__ __forceinline__ float group8_sum(float v) {
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    return v;
+}
+
+// 16 int8 codes -> 16 floats (exact)
+__device__ __forceinline__ void unpack16(const uint4& r, float (&v)[DPL]) {
+    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v[4 * i + b] = (float)(int)(int8_t)(w[i] >> (8 * b));
+    }
+}
+
+// double -> bf16 in ONE rounding (decode_cache.hip)
+__device__ __forceinline__ bf16_t d2bf(double y) {
+    float f = (float)y;
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0xffffu) == 0x8000u) {
+        const double r = y - (double)f;
+        if (r != 0.0) f = __uint_as_float((r > 0.0) == (f > 0.f) ? u + 1 : u - 1);
+    }
+    return f2bf(f);
+}
+
+// element d of the (optionally rotated) vector x[0..127]: x[d] c[d] + rotate_half(x)[d] s[d], rotate_half(x) = (-x[64..127], x[0..63])
+__device__ __forceinline__ double rotated(const bf16_t* x, const float* cs, const float* sn, int d) {
+    const double xd = (double)bf2f(x[d]);
+    if (!cs) return xd;
+    const double xp = (double)bf2f(x[d ^ 64]);
+    return xd * (double)cs[d] + (d < 64 ? -xp : xp) * (double)sn[d];
+}
+
+// one workgroup's share of a step: range `split` of row blockIdx.z, head blockIdx.y
+__device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int split, const int pos, const int nsplit, const int kps,
+                                                      const float* cs_tab, const float* sn_tab) {
+    __shared__ float qs[HD];                                        // scale * q'
+    __shared__ __attribute__((aligned(16))) int8_t code_new[2][HD]; // the new token's codes: [0] k', [1] v
+    __shared__ float scale_new[2], wave_amax[NT / OTTER_WAVE];
+    __shared__ float red_m[GROUPS], red_l[GROUPS], red_o[GROUPS][HD];
+    const int h = blockIdx.y, n = blockIdx.z, tid = threadIdx.x;
+    const int64_t nh = (int64_t)n * a.H + h;
+
+    // 1. the new token: threads 0..127 own q[d] and v[d] (waves 0, 1), threads 128..255 own k[d] (waves 2, 3).  x = what the bf16 cache
+    //    would store; amax over the 128 dims (a max: exact in any order), then divide and round.
+    {
+        const int d = tid & (HD - 1), which = tid < HD ? 1 : 0;
+        const float* cs = cs_tab ? cs_tab + n * a.cs_rs : nullptr;
+        const float* sn = cs_tab ? sn_tab + n * a.cs_rs : nullptr;
+        float x;
+        if (tid < HD) {
+            qs[d] = (float)rotated(a.q + n * a.q_rs + h * a.q_hs, cs, sn, d) * a.scale;
+            x = bf2f(a.vn[n * a.vn_rs + h * a.vn_hs + d]);
+        } else {
+            x = bf2f(d2bf(rotated(a.kn + n * a.kn_rs + h * a.kn_hs, cs, sn, d)));
+        }
+        const float wm = wave_max(fabsf(x));
+        if ((tid & (OTTER_WAVE - 1)) == 0) wave_amax[tid / OTTER_WAVE] = wm;
+        __syncthreads();
+        const float amax = fmaxf(wave_amax[tid < HD ? 0 : 2], wave_amax[tid < HD ? 1 : 3]);
+        const float sc = amax == 0.f ? 1.f : amax / 127.f;
+        const float c = fminf(fmaxf(rintf(x / sc), -127.f), 127.f);
+        code_new[which][d] = (int8_t)(int)c;
+        if (d == 0) scale_new[which] = sc;
+    }
+    __syncthreads();
+
+    const int l8 = tid & (LANES - 1), g = tid >> 3;
+    const int j0 = split * kps, j1 = min(j0 + kps, pos + 1);
+    // 2. the append (the workgroup whose range holds `pos`): slot [n, h, pos] of the caller's OWN row -- 8 lanes x 16 bytes each for the K and
+    //    the V codes, one lane each for the two scales
+    if (pos >= j0 && pos < j1) {
+        if (tid < 2 * LANES) {
+            int8_t* dst = (tid < LANES ? a.kc + n * a.kc_rs + h * a.kc_hs : a.vc + n * a.vc_rs + h * a.vc_hs) + (int64_t)pos * HD + DPL * l8;
+            *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&code_new[tid < LANES ? 0 : 1][DPL * l8]);
+        } else if (tid < 2 * LANES + 2) {
+            const int w = tid - 2 * LANES;
+            float* dst = w == 0 ? a.ks + n * a.ks_rs + h * a.ks_hs : a.vs + n * a.vs_rs + h * a.vs_hs;
+            dst[pos] = scale_new[w];
+        }
+    }
+
+    // 3. the workgroup's key range: scores, online softmax, P V.  Keys j < pos come from the cache (row src[n, j]); key pos from LDS.
+    float q[DPL];
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) q[i] = qs[DPL * l8 + i];
+    const int8_t* kb = a.kc + h * a.kc_hs + DPL * l8;
+    const int8_t* vb = a.vc + h * a.vc_hs + DPL * l8;
+    const float* ksb = a.ks + h * a.ks_hs;
+    const float* vsb = a.vs + h * a.vs_hs;
+    const int32_t* src = a.src ? a.src + n * a.src_rs : nullptr;
+    const uint8_t* kv = a.kvalid ? a.kvalid + n * a.kv_rs : nullptr;
+    const float slope = a.slopes ? a.slopes[h] : 0.f;
+    float m = -INFINITY, l = 0.f, acc[DPL];
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
+    for (int jb = j0; jb < j1; jb += KEYS_PER_ITER) {
+        uint4 kr[UNROLL], vr[UNROLL];
+        float ksc[UNROLL], vsc[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int j = jb + u * GROUPS + g;
+            if (j < j1 && j < pos) {
+                // a table entry outside [0, N) is clamped: it can make the result wrong, never an access outside the cache
+                const int64_t row = src ? (int64_t)min(max(src[j], 0), a.N - 1) : (int64_t)n;
+                kr[u] = *reinterpret_cast<const uint4*>(kb + row * a.kc_rs + (int64_t)j * HD);
+                vr[u] = *reinterpret_cast<const uint4*>(vb + row * a.vc_rs + (int64_t)j * HD);
+                ksc[u] = ksb[row * a.ks_rs + j];
+                vsc[u] = vsb[row * a.vs_rs + j];
+            } else if (j < j1) {                          // j == pos: the new token, as the cache now holds it
+                kr[u] = *reinterpret_cast<const uint4*>(&code_new[0][DPL * l8]);
+                vr[u] = *reinterpret_cast<const uint4*>(&code_new[1][DPL * l8]);
+                ksc[u] = scale_new[0];
+                vsc[u] = scale_new[1];
+            } else {
+                kr[u] = make_uint4(0, 0, 0, 0);
+                vr[u] = make_uint4(0, 0, 0, 0);
+                ksc[u] = 0.f;
+                vsc[u] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int j = jb + u * GROUPS + g;
+            const bool live = j < j1;
+            float k[DPL], v[DPL];
+            unpack16(kr[u], k);
+            unpack16(vr[u], v);
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < DPL; ++i) s = fmaf(q[i], k[i], s);
+            s = group8_sum(s);                            // (all lanes: the shuffles stay convergent)
+            s = fmaf(s, ksc[u], slope * (float)(j - pos));
+            if (!live || (kv && kv[j] == 0)) s = -INFINITY;
+            const float mn = fmaxf(m, s);
+            if (mn != -INFINITY) {
+                const float alpha = __expf(m - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
+                const float pv = p * vsc[u];
+                l = fmaf(l, alpha, p);
+#pragma unroll
+                for (int i = 0; i < DPL; ++i) acc[i] = fmaf(acc[i], alpha, pv * v[i]);
+                m = mn;
+            }
+        }
+    }
+
+    // 4. the 32 groups, in order
+    if (l8 == 0) { red_m[g] = m; red_l[g] = l; }
+#pragma unroll
+    for (int i = 0; i < DPL; ++i) red_o[g][DPL * l8 + i] = acc[i];
+    __syncthreads();
+    if (tid < HD) {
+        float M = -INFINITY;
+        for (int gg = 0; gg < GROUPS; ++gg) M = fmaxf(M, red_m[gg]);
+        float L = 0.f, O = 0.f;
+        if (M != -INFINITY) {
+            for (int gg = 0; gg < GROUPS; ++gg) {
+                const float f = red_m[gg] == -INFINITY ? 0.f : __expf(red_m[gg] - M);
+                L = fmaf(red_l[gg], f, L);
+                O = fmaf(red_o[gg][tid], f, O);
+            }
+        }
+        if (nsplit == 1) {
+            a.o[nh * HD + tid] = f2bf(L > 0.f ? O / L : 0.f);
+        } else {
+            float* pr = a.part + (nh * a.part_stride + split) * PART;
+            if (tid < 2) pr[tid] = tid == 0 ? M : L;
+            pr[2 + tid] = O;
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void decode_cached_i8_kernel(DqArgs a) {
+    decode_cached_i8_body(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
+}
+
+// nsplit > 1: one workgroup of 128 lanes per (head, row) combines the ranges in range order; p = the (row, head)'s first record
+__device__ __forceinline__ void decode_cached_i8_combine_body(const float* __restrict__ p, bf16_t* __restrict__ o, int64_t nh, int nsplit) {
+    const int d = threadIdx.x;
+    float M = -INFINITY;
+    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[s * PART]);
+    float L = 0.f, O = 0.f;
+    if (M != -INFINITY) {
+        for (int s = 0; s < nsplit; ++s) {
+            const float ms = p[s * PART];
+            const float f = ms == -INFINITY ? 0.f : __expf(ms - M);
+            L = fmaf(p[s * PART + 1], f, L);
+            O = fmaf(p[s * PART + 2 + d], f, O);
+        }
+    }
+    o[nh * HD + d] = f2bf(L > 0.f ? O / L : 0.f);
+}
+
+__global__ __launch_bounds__(HD) void decode_cached_i8_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
+    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
+    decode_cached_i8_combine_body(part + nh * nsplit * PART, o, nh, nsplit);
+}
+
+// ---- the position in device memory (decode_cache.hip): grid (max_ranges, H, N) for the capacity; a workgroup whose range is not live at the
+// current position, or any workgroup when the position is outside [1, S_max), returns before it touches memory or reaches a barrier --------
+__global__ __launch_bounds__(NT) void decode_cached_i8_dyn_kernel(DqArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus,
+                                                                  int64_t table_rs) {
+    const int pos = *pos_dev;
+    if (pos < 1 || pos >= S_max) return;
+    const DqSplit sp = dq_split((int64_t)pos + 1, (int64_t)a.N * a.H, cus);
+    if ((int)blockIdx.x >= sp.nsplit) return;
+    // row `pos` of the rotary tables, shared by every row (cs_rs = 0)
+    decode_cached_i8_body(a, blockIdx.x, pos, sp.nsplit, sp.kps, a.cs ? a.cs + (int64_t)pos * table_rs : nullptr,
+                          a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
+}
+
+__global__ __launch_bounds__(HD) void decode_cached_i8_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
+                                                                          const int32_t* __restrict__ pos_dev, int N, int H, int S_max, int cus,
+                                                                          int max_ranges) {
+    const int pos = *pos_dev;
+    if (pos < 1 || pos >= S_max) return;
+    const int nsplit = min(dq_split((int64_t)pos + 1, (int64_t)N * H, cus).nsplit, max_ranges);
+    if (nsplit == 1) return;                              // the one live workgroup wrote o itself
+    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
+    decode_cached_i8_combine_body(part + nh * max_ranges * PART, o, nh, nsplit);
+}
+
+int cu_count() {
+    static int counts[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (counts[dev] == 0) {
+        int n = 0;
+        counts[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    return counts[dev];
+}
+
+bool mult(int64_t m, int64_t a, int64_t b) { return a % m == 0 && b % m == 0; }
+
+}  // namespace
+
+// the argument checks both entry points share (NAME: the entry point's name in messages)
+#define DQ_REQUIRE_COMMON(NAME)                                                                                                                       \
+    OTTER_REQUIRE(head_dim == HD, NAME ": head_dim %ld (128 only)", (long)head_dim);                                                                 \
+    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, NAME ": bad shape N=%ld H=%ld", (long)N, (long)H);                                      \
+    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, NAME ": S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT);                           \
+    OTTER_REQUIRE((((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,                         \
+                  NAME ": q, k_new, v_new, k_cache, v_cache need 16-byte alignment");                                                                \
+    OTTER_REQUIRE((((uintptr_t)k_scale | (uintptr_t)v_scale) & 3) == 0, NAME ": k_scale, v_scale need 4-byte alignment");                             \
+    OTTER_REQUIRE(mult(8, q_row_stride, q_head_stride) && mult(8, k_new_row_stride, k_new_head_stride) && mult(8, v_new_row_stride, v_new_head_stride), \
+                  NAME ": q / k_new / v_new strides must be multiples of 8 elements");                                                               \
+    OTTER_REQUIRE(mult(16, k_cache_row_stride, k_cache_head_stride) && mult(16, v_cache_row_stride, v_cache_head_stride),                             \
+                  NAME ": code cache strides must be multiples of 16 elements");                                                                     \
+    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0,       \
+                  NAME ": a cache head stride below S_max * 128 would make the slots of two heads overlap");                                         \
+    OTTER_REQUIRE(k_scale_head_stride >= S_max && v_scale_head_stride >= S_max && k_scale_row_stride >= 0 && v_scale_row_stride >= 0,                 \
+                  NAME ": a scale head stride below S_max would make the scales of two heads overlap")
+
+#define DQ_FILL_ARGS(a)                                                                                                       \
+    a.q = (const bf16_t*)q; a.q_rs = q_row_stride; a.q_hs = q_head_stride;                                                    \
+    a.kn = (const bf16_t*)k_new; a.kn_rs = k_new_row_stride; a.kn_hs = k_new_head_stride;                                     \
+    a.vn = (const bf16_t*)v_new; a.vn_rs = v_new_row_stride; a.vn_hs = v_new_head_stride;                                     \
+    a.kc = (int8_t*)k_cache; a.kc_rs = k_cache_row_stride; a.kc_hs = k_cache_head_stride;                                     \
+    a.vc = (int8_t*)v_cache; a.vc_rs = v_cache_row_stride; a.vc_hs = v_cache_head_stride;                                     \
+    a.ks = k_scale; a.ks_rs = k_scale_row_stride; a.ks_hs = k_scale_head_stride;                                              \
+    a.vs = v_scale; a.vs_rs = v_scale_row_stride; a.vs_hs = v_scale_head_stride;                                              \
+    a.src = src; a.src_rs = src_row_stride; a.kvalid = key_valid; a.kv_rs = key_valid_row_stride; a.slopes = alibi_slopes;    \
+    a.o = (bf16_t*)o; a.part = (float*)workspace; a.N = (int)N; a.H = (int)H; a.scale = scale
+
+extern "C" {
+
+int otter_decode_attn_cached_i8(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                const float* cos_rows, const float* sin_rows, int64_t cos_row_stride, void* k_cache, int64_t k_cache_row_stride,
+                                int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride, int64_t v_cache_head_stride,
+                                float* k_scale, int64_t k_scale_row_stride, int64_t k_scale_head_stride, float* v_scale,
+                                int64_t v_scale_row_stride, int64_t v_scale_head_stride, const int32_t* src, int64_t src_row_stride,
+                                const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace,
+                                int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim, float scale,
+                                void* stream) {
+    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && k_scale && v_scale && o && workspace, "decode_attn_cached_i8: null pointer");
+    OTTER_REQUIRE((cos_rows == nullptr) == (sin_rows == nullptr),
+                  "decode_attn_cached_i8: cos_rows and sin_rows must both be given or both be NULL");
+    DQ_REQUIRE_COMMON("decode_attn_cached_i8");
+    OTTER_REQUIRE(pos >= 1, "decode_attn_cached_i8: pos=%ld: a cached step continues a cache (pos >= 1)", (long)pos);
+    OTTER_REQUIRE(pos < S_max, "decode_attn_cached_i8: pos=%ld is beyond the cache capacity S_max=%ld", (long)pos, (long)S_max);
+    OTTER_REQUIRE(cos_row_stride >= 0 && (!src || src_row_stride >= pos) && (!key_valid || key_valid_row_stride >= pos + 1),
+                  "decode_attn_cached_i8: src needs a row stride >= pos, key_valid one >= pos + 1, cos / sin a non-negative one");
+    const int64_t Sk = pos + 1;
+    const int64_t need = OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES(N, H, Sk);
+    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_i8: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+
+    const DqSplit sp = dq_split(Sk, N * H, cu_count());
+    const int64_t nsplit = sp.nsplit;
+
+    DqArgs a;
+    DQ_FILL_ARGS(a);
+    a.cs = cos_rows; a.sn = sin_rows; a.cs_rs = cos_row_stride;
+    a.pos = (int)pos; a.nsplit = (int)nsplit; a.kps = sp.kps; a.part_stride = (int)nsplit;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(decode_cached_i8_kernel, dim3((unsigned)nsplit, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a);
+    OTTER_CHECK_LAUNCH("decode_attn_cached_i8");
+    if (nsplit > 1) {
+        hipLaunchKernelGGL(decode_cached_i8_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o,
+                           (int)H, (int)nsplit);
+        OTTER_CHECK_LAUNCH("decode_attn_cached_i8 (combine)");
+    }
+    return OTTER_OK;
+}
+
+int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                    int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                    const float* cos_table, const float* sin_table, int64_t table_row_stride, void* k_cache,
+                                    int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                    int64_t v_cache_head_stride, float* k_scale, int64_t k_scale_row_stride, int64_t k_scale_head_stride,
+                                    float* v_scale, int64_t v_scale_row_stride, int64_t v_scale_head_stride, const int32_t* src,
+                                    int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes,
+                                    void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, const int32_t* pos_dev,
+                                    int64_t S_max, int64_t head_dim, float scale, void* stream) {
+    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && k_scale && v_scale && o && workspace && pos_dev,
+                  "decode_attn_cached_i8_dyn: null pointer");
+    OTTER_REQUIRE((cos_table == nullptr) == (sin_table == nullptr),
+                  "decode_attn_cached_i8_dyn: cos_table and sin_table must both be given or both be NULL");
+    DQ_REQUIRE_COMMON("decode_attn_cached_i8_dyn");
+    OTTER_REQUIRE(((uintptr_t)pos_dev & 3) == 0, "decode_attn_cached_i8_dyn: pos_dev needs 4-byte alignment");
+    // any position below S_max may be read from pos_dev: the tables, the beam table and the mask must hold the capacity
+    OTTER_REQUIRE((!cos_table || table_row_stride >= HD) && (!src || src_row_stride >= S_max - 1) && (!key_valid || key_valid_row_stride >= S_max),
+                  "decode_attn_cached_i8_dyn: cos / sin tables need a row stride >= 128, src one >= S_max - 1, key_valid one >= S_max");
+    const int64_t need = OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES(N, H, S_max);
+    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_i8_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+
+    // the CU count is looked up once per device (a step that is to be captured has run eagerly before: no device query under capture)
+    const int cus = cu_count();
+    const int64_t max_ranges = dq_max_ranges(S_max, N * H, cus);
+
+    DqArgs a;
+    DQ_FILL_ARGS(a);
+    a.cs = cos_table; a.sn = sin_table; a.cs_rs = 0;
+    a.pos = 0; a.nsplit = 0; a.kps = 0; a.part_stride = (int)max_ranges;   // (pos, nsplit, kps: read and derived on the device)
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(decode_cached_i8_dyn_kernel, dim3((unsigned)max_ranges, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a, pos_dev, (int)S_max,
+                       cus, table_row_stride);
+    OTTER_CHECK_LAUNCH("decode_attn_cached_i8_dyn");
+    if (max_ranges > 1) {
+        hipLaunchKernelGGL(decode_cached_i8_dyn_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace,
+                           (bf16_t*)o, pos_dev, (int)N, (int)H, (int)S_max, cus, (int)max_ranges);
+        OTTER_CHECK_LAUNCH("decode_attn_cached_i8_dyn (combine)");
+    }
+    return OTTER_OK;
+}
+
+}  // extern "C"

@@ -360,6 +360,9 @@ class PersimmonForCausalLM(PersimmonPreTrainedModel):
         from .generation import generate_tokens
 
         use_cache = bool(generate_kwargs.pop("use_cache", getattr(self.config, "use_cache", True)))
+        if generate_kwargs.pop("kv_cache_dtype", None) is not None:
+            raise NotImplementedError("PersimmonForCausalLM.generate: kv_cache_dtype quantises the static cache, which is not built for the "
+                                      "Persimmon host (head_dim 64)")
 
         def step(ids, mask, past, beam_idx):
             if use_cache and past is not None:
@@ -458,6 +461,9 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
         from .generation import generate_tokens
 
         use_cache = bool(generate_kwargs.pop("use_cache", getattr(self.config.text_config, "use_cache", True)))
+        if generate_kwargs.pop("kv_cache_dtype", None) is not None:
+            raise NotImplementedError("FuyuForCausalLM.generate: kv_cache_dtype quantises the static cache, which is not built for the "
+                                      "Persimmon host (head_dim 64)")
         cache_impl = generate_kwargs.pop("cache_implementation", None)
         if cache_impl == "static":
             raise NotImplementedError("FuyuForCausalLM.generate: cache_implementation='static' is not built for the Persimmon host (head_dim 64, "

@@ -26,6 +26,28 @@ The cached step runs on csrc/decode_cache.hip (`ops.decode_attn_cached`) on the 
 as query heads.  Everywhere else -- the CPU, fp32 compute, other head sizes -- `attend_reference` runs: a plain-torch restatement of exactly
 what the kernel does.  Like `Int8FrozenLinear`'s, that branch is a deliberate exception to "no PyTorch path": it is what makes the bookkeeping
 (the table, the append, the hosts' wiring) testable without a GPU, and it is the structure the kernel's oracle follows.
+
+The int8 form (`StaticKVCache(..., kv_dtype="int8")`, `generate(..., cache_implementation="static", kv_cache_dtype="int8")`): opt-in and
+lossy, like the int8 decoder.  Each cached vector is 128 int8 codes and one fp32 scale -- 132 bytes against 256:
+
+    k, v              int8 [n_layers, rows, n_heads, max_len, head_dim]
+    k_scale, v_scale  fp32 [n_layers, rows, n_heads, max_len]
+
+THE FORMAT.  For a vector x[head_dim] exactly as the unquantised cache stores it (a key after rotary, rounded once to the compute dtype; a
+value as projected), read as fp32:
+
+    amax  = max_i |x[i]|
+    scale = amax / 127                                        (fp32 IEEE division; 1 when amax == 0)
+    code  = clamp(rint_half_even(x[i] / scale), -127, 127)    as int8 (-128 never occurs)
+    value = float(code) * scale                               (what attention sees)
+
+which is the rule of `quant.quantize_weight_int8`, applied per (layer, row, head, position): `quantize_kv_int8`.  These are a handful of
+IEEE-exact operations, so torch on the CPU, torch on the GPU and csrc/decode_cache_i8.hip give the same codes and scales, bit for bit.  The
+scale is per token because an append knows only its own vector: no scale of an earlier position is ever rewritten, so the in-place
+invariant above carries over.  `fill` quantises the prompt with torch ops; a cached step quantises the new token as it appends it and
+attends to it in its dequantised form, so a step returns what "append, then attend over the cache" returns.  `dtype` stays the compute
+dtype (what `attend` and `to_legacy` return in).  The kernel conditions are those of the unquantised cache (`uses_kernel`); everywhere
+else `attend_reference` runs its int8 branch.
 """
 from __future__ import annotations
 
@@ -49,14 +71,37 @@ def cache_geometry(config):
             int(config.max_position_embeddings))
 
 
+def quantize_kv_int8(x: torch.Tensor):
+    """x [..., d] -> (codes int8 [..., d], scale fp32 [...]) by THE FORMAT of the module docstring: `quant.quantize_weight_int8` over the
+    last dim."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    # tensor / tensor: a true division on every backend (a Python-scalar divisor may be turned into a multiplication by its reciprocal)
+    scale = amax / torch.full_like(amax, 127.0)
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    return torch.round(xf / scale.unsqueeze(-1)).clamp_(-127, 127).to(torch.int8), scale
+
+
+def dequantize_kv_int8(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """float(code) * scale in fp32 at least, rounded once to `dtype`."""
+    ct = torch.float64 if dtype == torch.float64 else torch.float32
+    return (codes.to(ct) * scale.to(ct).unsqueeze(-1)).to(dtype)
+
+
 class StaticKVCache:
-    def __init__(self, n_layers: int, rows: int, n_heads: int, head_dim: int, max_len: int, device, dtype: torch.dtype = torch.bfloat16):
+    def __init__(self, n_layers: int, rows: int, n_heads: int, head_dim: int, max_len: int, device, dtype: torch.dtype = torch.bfloat16,
+                 kv_dtype: Optional[str] = None):
         if min(n_layers, rows, n_heads, head_dim) < 1 or max_len < 2:
             raise ValueError("StaticKVCache: n_layers, rows, n_heads, head_dim >= 1 and max_len >= 2")
+        if kv_dtype not in (None, "int8"):
+            raise ValueError("StaticKVCache: kv_dtype must be None or 'int8', got %r" % (kv_dtype,))
         self.n_layers, self.rows, self.n_heads, self.head_dim, self.max_len = int(n_layers), int(rows), int(n_heads), int(head_dim), int(max_len)
         shape = (self.n_layers, self.rows, self.n_heads, self.max_len, self.head_dim)
-        self.k = torch.zeros(shape, dtype=dtype, device=device)
-        self.v = torch.zeros(shape, dtype=dtype, device=device)
+        self.kv_dtype, self._dtype = kv_dtype, dtype
+        self.k = torch.zeros(shape, dtype=torch.int8 if self.int8 else dtype, device=device)
+        self.v = torch.zeros(shape, dtype=torch.int8 if self.int8 else dtype, device=device)
+        self.k_scale = torch.ones(shape[:-1], dtype=torch.float32, device=device) if self.int8 else None   # (a zero vector's scale is 1)
+        self.v_scale = torch.ones(shape[:-1], dtype=torch.float32, device=device) if self.int8 else None
         self.length = 0
         self.src: Optional[torch.Tensor] = None
         self.pos_dev: Optional[torch.Tensor] = None     # replay mode (enable_replay)
@@ -66,12 +111,21 @@ class StaticKVCache:
     # ---- bookkeeping ----------------------------------------------------------------------------------------------------------------
 
     @property
+    def int8(self) -> bool:
+        return self.kv_dtype == "int8"
+
+    @property
     def device(self):
         return self.k.device
 
     @property
     def dtype(self):
-        return self.k.dtype
+        """The compute dtype: what the unquantised cache stores, and what `attend` and `to_legacy` return in."""
+        return self._dtype
+
+    def nbytes(self) -> int:
+        """Bytes of the keys and values (codes and scales for the int8 form)."""
+        return sum(t.numel() * t.element_size() for t in (self.k, self.v, self.k_scale, self.v_scale) if t is not None)
 
     def get_seq_length(self) -> int:
         return self.length
@@ -80,6 +134,8 @@ class StaticKVCache:
         return self.n_layers
 
     def data_ptrs(self):
+        if self.int8:
+            return (self.k.data_ptr(), self.v.data_ptr(), self.k_scale.data_ptr(), self.v_scale.data_ptr())
         return (self.k.data_ptr(), self.v.data_ptr())
 
     def check_step(self, rows: int, S: int) -> None:
@@ -95,13 +151,20 @@ class StaticKVCache:
 
     def fill(self, layer: int, k: torch.Tensor, v: torch.Tensor) -> None:
         """Prefill: k, v indexed [rows, n_heads, S, head_dim] (any strides: the views the flash and SDPA paths produce) -> positions [0, S).
-        One strided copy per tensor."""
+        One strided copy per tensor.  int8: the prompt's vectors are rounded to the compute dtype first, so that the quantiser sees what
+        the unquantised cache would hold."""
         if self.length != 0:
             raise ValueError("StaticKVCache.fill: the cache is not empty")
         S = k.shape[2]
         want = (self.rows, self.n_heads, S, self.head_dim)
         if tuple(k.shape) != want or tuple(v.shape) != want or S > self.max_len:
             raise ValueError("StaticKVCache.fill: expected k, v %s with S <= %d, got %s / %s" % (want, self.max_len, tuple(k.shape), tuple(v.shape)))
+        if self.int8:
+            for codes, scales, t in ((self.k, self.k_scale, k), (self.v, self.v_scale, v)):
+                c, s = quantize_kv_int8(t.to(self.dtype))
+                codes[layer, :, :, :S].copy_(c)
+                scales[layer, :, :, :S].copy_(s)
+            return
         self.k[layer, :, :, :S].copy_(k)
         self.v[layer, :, :, :S].copy_(v)
 
@@ -156,16 +219,18 @@ class StaticKVCache:
             self.src[:, :L] = self.src[:, :L].index_select(0, beam_idx.to(self.device))
 
     def _gathered(self, t: torch.Tensor, upto: int) -> torch.Tensor:
-        """t [rows, H, max_len, d] -> [rows, H, upto, d]: position j of row n from row src[n, j]."""
+        """t [rows, H, max_len, d] -> [rows, H, upto, d]: position j of row n from row src[n, j].  (Scales: t [rows, H, max_len].)"""
         if self.src is None:
             return t[:, :, :upto]
         idx = self.src[:, :upto].long()                                        # [rows, upto]
         pos = torch.arange(upto, device=t.device).view(1, -1)
+        if t.dim() == 3:
+            return t[idx, :, pos].transpose(1, 2)                              # [rows, upto, H] -> [rows, H, upto]
         return t[idx, :, pos].permute(0, 2, 1, 3)                              # [rows, upto, H, d] -> [rows, H, upto, d]
 
     def to_legacy(self, host) -> tuple:
         """The tuple-of-tuples cache in the host's own layout, gathered through the table: "mpt" (or an MPT module) k [N,H,d,S], v [N,H,S,d];
-        "llama" k, v [N,H,S,d]."""
+        "llama" k, v [N,H,S,d].  int8: dequantised, in the compute dtype."""
         name = host if isinstance(host, str) else type(host).__name__
         mpt = "mpt" in name.lower()
         if not mpt and "llama" not in name.lower():
@@ -173,6 +238,9 @@ class StaticKVCache:
         out = []
         for i in range(self.n_layers):
             k, v = self._gathered(self.k[i], self.length), self._gathered(self.v[i], self.length)
+            if self.int8:
+                k = dequantize_kv_int8(k, self._gathered(self.k_scale[i], self.length), self.dtype)
+                v = dequantize_kv_int8(v, self._gathered(self.v_scale[i], self.length), self.dtype)
             out.append((k.transpose(2, 3) if mpt else k, v))
         return tuple(out)
 
@@ -193,6 +261,10 @@ class StaticKVCache:
             if self.uses_kernel(q, k_new.shape[1]):
                 from . import ops
 
+                if self.int8:
+                    return ops.decode_attn_cached_i8_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
+                                                         self.pos_dev, scale, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
+                                                         slopes=slopes)
                 return ops.decode_attn_cached_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.pos_dev, scale, cos_table=cos,
                                                   sin_table=sin, src=self.src, key_valid=self.valid, slopes=slopes)
             self.kernel_steps = False   # (the restatement reads the position back to the host: such a step cannot be captured)
@@ -200,6 +272,9 @@ class StaticKVCache:
         if self.uses_kernel(q, k_new.shape[1]):
             from . import ops
 
+            if self.int8:
+                return ops.decode_attn_cached_i8(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
+                                                 self.length, scale, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)
             return ops.decode_attn_cached(q, k_new, v_new, self.k[layer], self.v[layer], self.length, scale, cos=cos, sin=sin, src=self.src,
                                           key_valid=key_valid, slopes=slopes)
         return self.attend_reference(layer, q, k_new, v_new, scale, cos=cos, sin=sin, key_valid=key_valid, slopes=slopes)
@@ -208,7 +283,8 @@ class StaticKVCache:
         """What csrc/decode_cache.hip does, in plain torch on any device and dtype: rotary (fp32 at least, k rounded to the cache dtype once),
         append at slot `length` of the row's own row, gather keys 0..length through the table, ALiBi slope * (j - length), padding mask,
         softmax in fp32 at least, a fully masked row -> 0.  Replay mode: the position is read from `pos_dev` (not from `length`), cos / sin
-        are the whole tables, of which row `pos` is taken, and the mask is columns 0..pos of `valid`."""
+        are the whole tables, of which row `pos` is taken, and the mask is columns 0..pos of `valid`.  int8 (csrc/decode_cache_i8.hip): the
+        rounded k and v are quantised, codes and scales stored, and the gathered codes dequantised -- key `pos` included."""
         pos, N, H, d = self.length, q.shape[0], q.shape[1], q.shape[2]
         if self.replay:
             pos = int(self.pos_dev.item())
@@ -230,10 +306,16 @@ class StaticKVCache:
                 c, s = c[:, None], s[:, None]
             qf = qf * c + rotate_half(qf) * s
             kf = kf * c + rotate_half(kf) * s
-        self.k[layer, :, :, pos] = kf.to(self.dtype)
-        self.v[layer, :, :, pos] = v_new.to(self.dtype)
-        k = self._gathered(self.k[layer], pos + 1).to(ct)                      # column pos of the table is the row's own index
-        v = self._gathered(self.v[layer], pos + 1).to(ct)
+        if self.int8:
+            self.k[layer, :, :, pos], self.k_scale[layer, :, :, pos] = quantize_kv_int8(kf.to(self.dtype))
+            self.v[layer, :, :, pos], self.v_scale[layer, :, :, pos] = quantize_kv_int8(v_new.to(self.dtype))
+            k = dequantize_kv_int8(self._gathered(self.k[layer], pos + 1), self._gathered(self.k_scale[layer], pos + 1), ct)
+            v = dequantize_kv_int8(self._gathered(self.v[layer], pos + 1), self._gathered(self.v_scale[layer], pos + 1), ct)
+        else:
+            self.k[layer, :, :, pos] = kf.to(self.dtype)
+            self.v[layer, :, :, pos] = v_new.to(self.dtype)
+            k = self._gathered(self.k[layer], pos + 1).to(ct)                  # column pos of the table is the row's own index
+            v = self._gathered(self.v[layer], pos + 1).to(ct)
         if k.shape[1] != H:
             k, v = k.repeat_interleave(H // k.shape[1], dim=1), v.repeat_interleave(H // v.shape[1], dim=1)
         s_ = torch.einsum("nhd,nhjd->nhj", qf * scale, k)

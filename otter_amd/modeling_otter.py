@@ -637,7 +637,9 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         `use_cache` selects between the two decode modes of SURVEY.md section 3.2 (default: the LM config's use_cache, False
         for OTTER-MPT7B).  `cache_implementation="static"` (implies use_cache) keeps the keys and values in one preallocated
         StaticKVCache (otter_amd/kv_cache.py): a step appends in place and beam search reorders an int32 table instead of the cache;
-        None or "dynamic" is the growing tuple cache.  `cross_attention_cache=True` (needs a cached mode) makes every cached step return
+        None or "dynamic" is the growing tuple cache.  `kv_cache_dtype="int8"` (needs cache_implementation="static") stores that cache as
+        int8 codes with one fp32 scale per cached vector, 0.516 of the bytes (kv_cache.py: an opt-in, lossy format, like the int8 decoder;
+        csrc/decode_cache_i8.hip quantises as it appends and dequantises as it attends).  `cross_attention_cache=True` (needs a cached mode) makes every cached step return
         what the last position of the full re-forward returns: a MediaCache (otter_amd/media_cache.py) carries each row's <image> count and
         the projected media, so the step attends to the image instead of reproducing the reference's zero; without it every path is
         unchanged.  `graph_decode=True` (needs cache_implementation="static" AND cross_attention_cache=True) captures one cached step
@@ -657,6 +659,11 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             raise ValueError("generate: cache_implementation must be None, 'dynamic' or 'static', got %r" % (cache_impl,))
         static = cache_impl == "static"
         use_cache = use_cache or static
+        kv_cache_dtype = generate_kwargs.pop("kv_cache_dtype", None)
+        if kv_cache_dtype not in (None, "int8"):
+            raise ValueError("generate: kv_cache_dtype must be None or 'int8', got %r" % (kv_cache_dtype,))
+        if kv_cache_dtype is not None and not static:
+            raise ValueError("generate: kv_cache_dtype='int8' needs cache_implementation='static'")
         media = [None]                                       # the MediaCache of this call, created beside the KV cache
         want_media = bool(generate_kwargs.pop("cross_attention_cache", False))
         graph_decode = bool(generate_kwargs.pop("graph_decode", False))
@@ -679,7 +686,8 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             n_layers, n_kv, head_dim, host_max = cache_geometry(lm.config)
             max_len = min(resolve_max_length(lang_x.shape[1], generate_kwargs.get("max_new_tokens"), generate_kwargs.get("max_length")), host_max)
             emb = lm.get_input_embeddings().weight
-            return StaticKVCache(n_layers, ids.shape[0], n_kv, head_dim, max(max_len, ids.shape[1] + 1), emb.device, OF.compute_dtype_for(emb))
+            return StaticKVCache(n_layers, ids.shape[0], n_kv, head_dim, max(max_len, ids.shape[1] + 1), emb.device, OF.compute_dtype_for(emb),
+                                 kv_dtype=kv_cache_dtype)
 
         def media_kw(ids, past, beam_idx):
             if media[0] is None:

@@ -663,6 +663,115 @@ def decode_attn_cached_dyn(q, k_new, v_new, k_cache, v_cache, pos_dev, scale, co
     return o
 
 
+def decode_attn_cached_i8_workspace_bytes(N: int, H: int, Sk: int) -> int:
+    """OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES of include/otter_hip.h."""
+    return N * H * ((Sk + 127) // 128) * 130 * 4
+
+
+def decode_attn_cached_i8_dyn_workspace_bytes(N: int, H: int, S_max: int) -> int:
+    """OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES of include/otter_hip.h."""
+    return N * H * ((S_max + 127) // 128) * 130 * 4
+
+
+def _decode_i8_common(name, q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, slopes):
+    """The checks both int8-cache entry points share; returns (N, H, S_max)."""
+    if q.dim() != 3:
+        raise K.OtterHipError(f"{name}: q must be [N,H,128]")
+    N, H = q.shape[:2]
+    if not (_decode_new_ok(q, N, H) and _decode_new_ok(k_new, N, H) and _decode_new_ok(v_new, N, H)):
+        raise K.OtterHipError(f"{name}: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
+    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
+    for t in (k_cache, v_cache):
+        if (t.dtype != torch.int8 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 128) or t.stride(3) != 1 or t.stride(2) != 128
+                or t.stride(0) % 16 or t.stride(1) % 16 or t.stride(1) < S_max * 128 or t.data_ptr() % 16):
+            raise K.OtterHipError(f"{name}: k_cache / v_cache must be int8 [N,H,S_max,128] with key stride 128, unit dim stride, 16-B aligned")
+    for t in (k_scale, v_scale):
+        if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape) != (N, H, S_max) or t.stride(2) != 1 or t.stride(1) < S_max:
+            raise K.OtterHipError(f"{name}: k_scale / v_scale must be fp32 [N,H,S_max] with a unit key stride")
+    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
+        raise K.OtterHipError(f"{name}: slopes must be contiguous fp32 [H]")
+    return N, H, S_max
+
+
+def decode_attn_cached_i8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos, scale, cos=None, sin=None, src=None, key_valid=None,
+                          slopes=None):
+    """decode_attn_cached over an int8 cache (otter_decode_attn_cached_i8): k_cache / v_cache int8 codes [N,H,S_max,128] (key stride 128,
+    strides % 16 == 0, 16-B aligned) and k_scale / v_scale fp32 [N,H,S_max] (unit key stride), all four written in place at slot `pos`
+    with the quantised new token, which is attended in its dequantised form.  Everything else as decode_attn_cached.
+    Returns o [N,H*128] bf16."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cos, sin, src, key_valid, slopes)
+    N, H, S_max = _decode_i8_common("decode_attn_cached_i8", q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, slopes)
+    pos = int(pos)
+    if S_max > DECODE_CACHED_MAX_KEYS or pos < 1 or pos >= S_max:
+        raise K.OtterHipError(f"decode_attn_cached_i8: pos={pos} outside [1, S_max) with S_max={S_max} (limit {DECODE_CACHED_MAX_KEYS})")
+    if (cos is None) != (sin is None):
+        raise K.OtterHipError("decode_attn_cached_i8: cos and sin must both be given or both be None")
+    cs_stride = 0
+    if cos is not None:
+        for t in (cos, sin):
+            if (t.dtype != torch.float32 or t.shape[-1] != 128 or t.stride(-1) != 1 or tuple(t.shape) not in ((128,), (N, 128))
+                    or tuple(t.shape) != tuple(cos.shape) or t.stride() != cos.stride()):
+                raise K.OtterHipError("decode_attn_cached_i8: cos / sin must be fp32 [128] or [N,128] with a unit dim stride and equal strides")
+        cs_stride = cos.stride(0) if cos.dim() == 2 else 0
+    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < pos or src.stride(1) != 1):
+        raise K.OtterHipError("decode_attn_cached_i8: src must be int32 [N, >= pos] with a unit column stride")
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < pos + 1
+                                  or key_valid.stride(1) != 1):
+        raise K.OtterHipError("decode_attn_cached_i8: key_valid must be uint8 [N, >= pos+1] with a unit column stride")
+    o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
+    ws = _ws.get(decode_attn_cached_i8_workspace_bytes(N, H, pos + 1), q.device)
+    K.check(K.lib().otter_decode_attn_cached_i8(
+        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
+        v_new.stride(1), K.ptr(cos), K.ptr(sin), cs_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(),
+        v_cache.stride(0), v_cache.stride(1), k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1), v_scale.data_ptr(), v_scale.stride(0),
+        v_scale.stride(1), K.ptr(src), src.stride(0) if src is not None else 0, K.ptr(key_valid),
+        key_valid.stride(0) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 128,
+        float(scale), K.stream()), "decode_attn_cached_i8")
+    return o
+
+
+def decode_attn_cached_i8_dyn(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos_dev, scale, cos_table=None, sin_table=None, src=None,
+                              key_valid=None, slopes=None, out=None):
+    """decode_attn_cached_dyn over an int8 cache (otter_decode_attn_cached_i8_dyn): the caches and scales of decode_attn_cached_i8, every
+    other argument as decode_attn_cached_dyn.  Returns o [N,H*128] bf16 (`out`: a contiguous bf16 [N,H*128] tensor to write instead)."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos_dev, cos_table, sin_table, src, key_valid, slopes, out)
+    N, H, S_max = _decode_i8_common("decode_attn_cached_i8_dyn", q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, slopes)
+    if S_max < 2 or S_max > DECODE_CACHED_MAX_KEYS:
+        raise K.OtterHipError(f"decode_attn_cached_i8_dyn: S_max={S_max} outside [2, {DECODE_CACHED_MAX_KEYS}]")
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
+        raise K.OtterHipError("decode_attn_cached_i8_dyn: pos_dev must be an int32 tensor of one element")
+    if (cos_table is None) != (sin_table is None):
+        raise K.OtterHipError("decode_attn_cached_i8_dyn: cos_table and sin_table must both be given or both be None")
+    tab_stride = 0
+    if cos_table is not None:
+        for t in (cos_table, sin_table):
+            if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != 128 or t.stride(1) != 1 or t.stride(0) < 128
+                    or t.stride() != cos_table.stride()):
+                raise K.OtterHipError("decode_attn_cached_i8_dyn: cos_table / sin_table must be fp32 [>= S_max, 128] with a unit dim stride and equal strides")
+        tab_stride = cos_table.stride(0)
+    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < S_max - 1 or src.stride(1) != 1
+                            or (N > 1 and src.stride(0) < S_max - 1)):
+        raise K.OtterHipError("decode_attn_cached_i8_dyn: src must be int32 [N, >= S_max - 1] with a unit column stride")
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < S_max
+                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < S_max)):
+        raise K.OtterHipError("decode_attn_cached_i8_dyn: key_valid must be uint8 [N, >= S_max] with a unit column stride")
+    if out is None:
+        o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * 128) or not out.is_contiguous():
+        raise K.OtterHipError("decode_attn_cached_i8_dyn: out must be a contiguous bf16 [N, H*128] tensor")
+    else:
+        o = out
+    ws = _ws.get(decode_attn_cached_i8_dyn_workspace_bytes(N, H, S_max), q.device)
+    K.check(K.lib().otter_decode_attn_cached_i8_dyn(
+        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
+        v_new.stride(1), K.ptr(cos_table), K.ptr(sin_table), tab_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1),
+        v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1), v_scale.data_ptr(),
+        v_scale.stride(0), v_scale.stride(1), K.ptr(src), max(src.stride(0), S_max - 1) if src is not None else 0, K.ptr(key_valid),
+        max(key_valid.stride(0), S_max) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H,
+        pos_dev.data_ptr(), S_max, 128, float(scale), K.stream()), "decode_attn_cached_i8_dyn")
+    return o
+
+
 XATTN_DECODE_MAX_KEYS = 65536          # include/otter_hip.h: M = T_img * n_per_media <= 65536
 
 
