@@ -818,7 +818,20 @@ ATTN_CASES = [
     (3, 8, 520, 64, 64, 1),
     (2, 4, 200, 192, 64, 2),
     (1, 2, 70, 96, 32, 1),
+    # masked split-K on the VALU kernels (Tq <= 64 and M > 256), 5 key tiles of 64 on the MFMA kernels: waves / tiles that see no allowed key
+    (2, 2, 40, 320, 64, 1),
+    (2, 2, 40, 320, 64, 2),
+    # split-K with Tq > 64 (B*H*ceil(Tq/256) = 1*4*2 = 8 < 64, M = 256 >= 256): 5 query blocks of 64, the last with 300 - 256 = 44 live rows
+    (1, 4, 300, 256, 64, 1),
+    # n % 32 != 0: all three dtypes run the VALU split-K kernels; 33 media, M % 32 = 8 -> a tail chunk of 8 keys
+    (1, 2, 70, 264, 8, 2),
+    (1, 2, 70, 264, 8, 1),
+    # unmasked split-K, M % 32 = 12: ceil(300/32) = 10 chunks over 4 waves -> waves 2 and 3 idle in the third iteration
+    (1, 2, 16, 300, 1, 0),
 ]
+
+# seed offsets of the cases whose default draw (seed = sum(case)) lacks a zeroed row (tt == 0) or a uniform row (tt == t_img + 1)
+ATTN_SEED_OFFSET = {(1, 2, 70, 264, 8, 2): 2, (1, 2, 70, 264, 8, 1): 3}
 
 
 @pytest.mark.parametrize("case", ATTN_CASES)
@@ -835,7 +848,7 @@ def test_attention_core(ops, case, dt):
 
 def _attention_core_case(ops, case, dt):
     B, H, Tq, M, n, mode = case
-    r = rng(sum(case))
+    r = rng(sum(case) + ATTN_SEED_OFFSET.get(case, 0))
     tdt = torch.float32 if dt == "f32" else torch.bfloat16
     inner = H * 64
     q = r.standard_normal((B, Tq, inner)).astype(np.float32)
@@ -848,6 +861,8 @@ def _attention_core_case(ops, case, dt):
         t_img = M // n
         ttn = r.integers(0, t_img + 2, size=(B, Tq))  # includes 0 (zeroed rows) and t_img+1 (fully masked -> uniform)
         ttn = np.sort(ttn, axis=1)
+        if M >= 256:    # the split-K / many-tile cases: zeroed rows, uniform rows and rows whose media follows fully masked tiles are all present
+            assert (ttn == 0).any() and (ttn == t_img + 1).any() and (ttn >= 3).any(), case
         tt = torch.from_numpy(ttn.astype(np.int32)).to(DEV)
     else:
         ttn = None
