@@ -478,13 +478,14 @@ int otter_xattn_decode(const void* q, int64_t q_stride, const void* k, const voi
  * Int8 weight-only products of the frozen decoder during generation (the reference's serving worker offers load_in_8bit for the
  * same model: pipeline/serve/model_worker.py:92-94).  Format: qweight int8 [N, K] row-major with row stride ldw, scale fp32 [N]:
  * scale[n] = max_k |W[n,k]| / 127 (1 for an all-zero row), q[n,k] = clamp(round_half_even(W[n,k] / scale[n]), -127, 127).
- *   otter_gemv_w8   y[M, N] = (x[M, K] . q[N, K]^T) * scale[N] (+ bias[N]) (then the exact-erf GELU when act == 1), 1 <= M <= 16:
- *       the linears of a cached decode step.  x bf16 (row stride ldx), y bf16 or fp32 (row stride ldy; only the M x N block is
+ *   otter_gemv_w8   y[M, N] = (x[M, K] . q[N, K]^T) * scale[N] (+ bias[N]), then the activation `act`, 1 <= M <= 16: the linears of a
+ *       cached decode step.  act: 0 none, 1 the exact-erf GELU (MPT), 3 the squared ReLU relu(v)^2 of the Persimmon MLP, evaluated in
+ *       fp32 on the fp32 value v and rounded once to y's dtype; every other code (2 included) is an argument error.  x bf16 (row stride ldx), y bf16 or fp32 (row stride ldy; only the M x N block is
  *       written), bias bf16 / fp32 or NULL.  x is not quantised; q is converted to bf16 (exact) and accumulated in fp32, the scale
  *       multiplies the finished fp32 sum, then bias, then activation.  N >= 1, K % 16 == 0, ldw % 16 == 0, ldx % 8 == 0; x, qweight,
  *       y 16-byte aligned.  workspace: at least OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K) bytes (fp32 split-K partials, combined in
  *       a fixed order: two calls on the same inputs give the same bits).
- *   otter_gemm_w8_rows   the same product, arguments and rules for 1 <= M <= 64: the linears of a one-token step of 17 to 64 rows
+ *   otter_gemm_w8_rows   the same product, arguments, `act` codes and rules for 1 <= M <= 64: the linears of a one-token step of 17 to 64 rows
  *       (batch x beams).  The weight is still streamed once; x is shared by a workgroup through LDS.  workspace: at least
  *       OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES(M, N, K) bytes.  The K split and with it the summation order of every output element
  *       depend on (N, K) only: two calls give the same bits, and row m of y has the same bits whatever M is and whatever the other

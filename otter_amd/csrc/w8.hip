@@ -2,8 +2,8 @@
 //
 // Format (otter_amd/quant.py): qweight int8 [N, K] row-major, scale fp32 [N] (one per output row), |q| <= 127.
 //
-// otter_gemv_w8   y[M, N] = (x[M, K] . q[N, K]^T) * scale[N] (+ bias[N]) (then exact-erf GELU), 1 <= M <= 16: one cached decode step sends
-//                 B x num_beams rows through every decoder linear, so the product is a single pass over the weight.  x is NOT quantised
+// otter_gemv_w8   y[M, N] = (x[M, K] . q[N, K]^T) * scale[N] (+ bias[N]) (then exact-erf GELU, act 1, or the squared ReLU of the Persimmon MLP,
+//                 act 3), 1 <= M <= 16: one cached decode step sends B x num_beams rows through every decoder linear, so the product is a single pass over the weight.  x is NOT quantised
 //                 and the i8 matrix instruction is not used: q is converted to bf16 in registers (exact for |q| <= 127) and fed to
 //                 v_mfma_f32_16x16x32_bf16 with x padded to 16 rows; fp32 accumulation, the scale applied to the fp32 sum.
 // otter_gemm_w8_rows  the same product for 1 <= M <= 64: one-token steps of 17 to 64 rows (B x num_beams) still stream the weight once.
@@ -72,7 +72,12 @@ __device__ __forceinline__ w8_bf16x8_t cvt8(uint32_t lo, uint32_t hi) {
 __device__ __forceinline__ float w8_epilogue(float v, int64_t n, const W8Args& a) {
     v *= a.scale[n];
     if (a.bias) v += ld_as_f32(a.bias, n, a.bias_dtype);
-    return a.act ? gelu_erf(v) : v;
+    if (a.act == 1) return gelu_erf(v);
+    if (a.act == 3) {                     // relu(v)^2 in fp32 on the fp32 sum: one rounding, to the output dtype, in the caller's store
+        const float r = fmaxf(v, 0.f);
+        return r * r;
+    }
+    return v;
 }
 
 template <int R>
@@ -326,7 +331,7 @@ int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, 
     OTTER_REQUIRE(ldw >= K && ldx >= K && ldy >= N, "gemv_w8: a leading dimension is smaller than the row it holds");
     OTTER_REQUIRE((y_dtype == OTTER_F32 || y_dtype == OTTER_BF16) && (!bias || bias_dtype == OTTER_F32 || bias_dtype == OTTER_BF16),
                   "gemv_w8: y / bias dtype must be OTTER_F32 or OTTER_BF16");
-    OTTER_REQUIRE(act == 0 || act == 1, "gemv_w8: act=%d (0 none, 1 GELU)", act);
+    OTTER_REQUIRE(act == 0 || act == 1 || act == 3, "gemv_w8: act=%d (0 none, 1 GELU, 3 squared ReLU)", act);
     const int64_t need = OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K);
     OTTER_REQUIRE(workspace_bytes >= need, "gemv_w8: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
 
@@ -368,7 +373,7 @@ int otter_gemm_w8_rows(const void* x, int64_t ldx, const void* qweight, int64_t 
     OTTER_REQUIRE(ldw >= K && ldx >= K && ldy >= N, "gemm_w8_rows: a leading dimension is smaller than the row it holds");
     OTTER_REQUIRE((y_dtype == OTTER_F32 || y_dtype == OTTER_BF16) && (!bias || bias_dtype == OTTER_F32 || bias_dtype == OTTER_BF16),
                   "gemm_w8_rows: y / bias dtype must be OTTER_F32 or OTTER_BF16");
-    OTTER_REQUIRE(act == 0 || act == 1, "gemm_w8_rows: act=%d (0 none, 1 GELU)", act);
+    OTTER_REQUIRE(act == 0 || act == 1 || act == 3, "gemm_w8_rows: act=%d (0 none, 1 GELU, 3 squared ReLU)", act);
     const int64_t need = OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES(M, N, K);
     OTTER_REQUIRE(workspace_bytes >= need, "gemm_w8_rows: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
 

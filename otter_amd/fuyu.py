@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import math
 import os
+import sys
 from typing import List, Optional
 
 import torch
@@ -55,6 +56,24 @@ def _cfg_get(cfg, name, default=None):
     return default if v is None else v
 
 
+def _is_int8(m) -> bool:
+    """isinstance(m, quant.Int8FrozenLinear) without importing otter_amd.quant: a model that was never quantised never loads that module."""
+    q = sys.modules.get(__package__ + ".quant")
+    return q is not None and isinstance(m, q.Int8FrozenLinear)
+
+
+def _linear(mod, x):
+    """A decoder linear: the quantised module itself (otter_amd/quant.py: no `weight` to read), else OF.trainable_linear as ever."""
+    return mod(x) if _is_int8(mod) else OF.trainable_linear(mod, x)
+
+
+def _refuse_save_if_int8(model):
+    quant = sys.modules.get(__package__ + ".quant")          # (not loaded: nothing was ever quantised)
+    if quant is not None and any(isinstance(m, quant.Int8FrozenLinear) for m in model.modules()):
+        raise RuntimeError("save_pretrained: the decoder of this model was quantised in memory (quantize_decoder_int8); its state_dict is "
+                           "not a reference-format checkpoint.  Save the model before quantising it.")
+
+
 class PersimmonMLP(nn.Module):
     def __init__(self, config: PersimmonConfig):
         super().__init__()
@@ -64,6 +83,10 @@ class PersimmonMLP(nn.Module):
         self.dense_4h_to_h = nn.Linear(config.intermediate_size, config.hidden_size)
 
     def forward(self, x):
+        up, dn = self.dense_h_to_4h, self.dense_4h_to_h
+        if _is_int8(up) or _is_int8(dn):        # int8 decoder (otter_amd/quant.py): relu(h)^2 in the first product's epilogue
+            h = up(x, act="relu2") if _is_int8(up) else torch.square(F.relu(OF.trainable_linear(up, x)))
+            return _linear(dn, h)
         # relu(h)^2 and the second Linear in one autograd node: the activation's backward rides in the input-gradient GEMM's tail
         return OF.sqrelu_linear(self.dense_4h_to_h, OF.trainable_linear(self.dense_h_to_4h, x))
 
@@ -110,23 +133,23 @@ class PersimmonAttention(nn.Module):
         cache append and the single-query attention in one kernel (csrc/persimmon_decode.hip), then `dense`.  The past is read, never
         written: the new cache is a fresh [B,H,S_past+1,64] pair, as the plain path's torch.cat makes it."""
         B = x.shape[0]
-        qkv = OF.trainable_linear(self.query_key_value, x)                      # [B,1,H*3*64]
+        qkv = _linear(self.query_key_value, x)                      # [B,1,H*3*64]
         gq, bq, gk, bk = self._ln_f32()
         o, k, v = ops.persimmon_decode_attn(qkv.view(B, self.n_heads, 3, 64), gq, bq, gk, bk, cos_row, sin_row, past_key_value[0],
                                             past_key_value[1], key_valid, self.rot, self.q_layernorm.eps, self.scale)
-        return OF.trainable_linear(self.dense, o.view(B, 1, self.hidden)), ((k, v) if use_cache else None)
+        return _linear(self.dense, o.view(B, 1, self.hidden)), ((k, v) if use_cache else None)
 
     def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False, key_valid=None):
         B, S, _ = x.shape
         H, d = self.n_heads, self.head_dim
-        qkv = OF.trainable_linear(self.query_key_value, x)                      # [B,S,H*3*d], per head (q | k | v)
+        qkv = _linear(self.query_key_value, x)                      # [B,S,H*3*d], per head (q | k | v)
         if hip:
             kw = {} if key_valid is None else {"key_valid": key_valid}
             if use_cache:
                 ctx, k, v = OF.persimmon_attention(qkv, self.q_layernorm, self.k_layernorm, cos, sin, H, self.rot, self.scale, want_kv=True, **kw)
-                return OF.trainable_linear(self.dense, ctx), (k, v)
+                return _linear(self.dense, ctx), (k, v)
             ctx = OF.persimmon_attention(qkv, self.q_layernorm, self.k_layernorm, cos, sin, H, self.rot, self.scale, **kw)
-            return OF.trainable_linear(self.dense, ctx), None
+            return _linear(self.dense, ctx), None
         q5 = qkv.view(B, S, H, 3, d)
         q, k, v = q5[..., 0, :], q5[..., 1, :], q5[..., 2, :]
         if self.qk_layernorm:
@@ -339,10 +362,13 @@ class PersimmonForCausalLM(PersimmonPreTrainedModel):
         return self.model
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, labels=None,
-                use_cache=None, return_dict=True, **unused):
+                use_cache=None, return_dict=True, _last_position_only=False, **unused):
+        """`_last_position_only` (private; generate() passes it when `lm_head` is quantised): un-embed only the last position, logits
+        [B, 1, V] -- a quantised un-embedding then runs as a GEMV / rows product on the prompt pass too instead of dequantising itself."""
         out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, past_key_values=past_key_values,
                          inputs_embeds=inputs_embeds, use_cache=use_cache)
-        logits = OF.trainable_linear(self.lm_head, out.last_hidden_state)
+        h = out.last_hidden_state
+        logits = _linear(self.lm_head, h[:, -1:, :] if _last_position_only else h)
         loss = None
         if labels is not None:
             lab = torch.full_like(labels, -100)
@@ -364,16 +390,37 @@ class PersimmonForCausalLM(PersimmonPreTrainedModel):
             raise NotImplementedError("PersimmonForCausalLM.generate: kv_cache_dtype quantises the static cache, which is not built for the "
                                       "Persimmon host (head_dim 64)")
 
+        kw = {"_last_position_only": True} if _is_int8(self.lm_head) else {}
+
         def step(ids, mask, past, beam_idx):
             if use_cache and past is not None:
                 if beam_idx is not None:
                     past = tuple(tuple(t.index_select(0, beam_idx) for t in layer) for layer in past)
-                out = self(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True)
+                out = self(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True, **kw)
             else:
-                out = self(input_ids=ids, attention_mask=mask, use_cache=use_cache)
+                out = self(input_ids=ids, attention_mask=mask, use_cache=use_cache, **kw)
             return out.logits[:, -1, :], (out.past_key_values if use_cache else None)
 
         return generate_tokens(step, input_ids, attention_mask, **generate_kwargs)
+
+    def quantize_decoder_int8(self, lm_head: bool = True) -> dict:
+        """Opt-in, for generation: hold the decoder's linears (`query_key_value`, `dense`, `dense_h_to_4h`, `dense_4h_to_h` of every layer)
+        and, with `lm_head`, the untied un-embedding as int8 weights with one fp32 scale per output row (otter_amd/quant.py:
+        `quantize_persimmon_decoder`), put the model in eval mode and return {"replaced", "bytes_before", "bytes_after"}.  The layers are
+        quantised whatever their requires_grad is: the call states that training is over.
+
+        This is an IN-MEMORY transformation done after loading: checkpoints stay in the reference's format.  `state_dict()` of a quantised
+        model (qweight / scale buffers instead of weights) is not a reference-format checkpoint, so `save_pretrained` on it raises; the
+        quantised decoder is inference-only (no autograd through it).  Calling it again replaces nothing."""
+        from .quant import quantize_persimmon_decoder
+
+        info = quantize_persimmon_decoder(self, lm_head=lm_head)
+        self.eval()
+        return info
+
+    def save_pretrained(self, *args, **kwargs):
+        _refuse_save_if_int8(self)
+        return super().save_pretrained(*args, **kwargs)
 
 
 class FuyuPreTrainedModel(PreTrainedModel):
@@ -480,22 +527,36 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
             patches = (patches.repeat_interleave(nb, dim=0) if torch.is_tensor(patches) else [p for p in patches for _ in range(nb)])
             idx0 = idx0.repeat_interleave(nb, dim=0)
 
+        kw = {"_last_position_only": True} if _is_int8(self.language_model.lm_head) else {}
+
         def step(ids, mask, past, beam_idx):
             if use_cache and past is not None:
                 if beam_idx is not None:
                     past = tuple(tuple(t.index_select(0, beam_idx) for t in layer) for layer in past)
-                out = self(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True)
+                out = self(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True, **kw)
             else:
                 idx = idx0
                 if idx is not None and ids.shape[1] > L0:
                     idx = torch.cat([idx, idx.new_full((idx.shape[0], ids.shape[1] - L0), -1)], dim=1)
-                out = self(input_ids=ids, image_patches=patches, image_patches_indices=idx, attention_mask=mask, use_cache=use_cache)
+                out = self(input_ids=ids, image_patches=patches, image_patches_indices=idx, attention_mask=mask, use_cache=use_cache, **kw)
             return out.logits[:, -1, :], (out.past_key_values if use_cache else None)
 
         return generate_tokens(step, input_ids, attention_mask, **generate_kwargs)
 
+    def quantize_decoder_int8(self, lm_head: bool = True) -> dict:
+        """`PersimmonForCausalLM.quantize_decoder_int8` on `language_model` (same contract: in-memory, eval mode, inference-only,
+        `save_pretrained` raises afterwards, a second call replaces nothing); `vision_embed_tokens` and the embedding stay as they are.
+        Returns {"replaced", "bytes_before", "bytes_after"}."""
+        info = self.language_model.quantize_decoder_int8(lm_head=lm_head)
+        self.eval()
+        return info
+
+    def save_pretrained(self, *args, **kwargs):
+        _refuse_save_if_int8(self)
+        return super().save_pretrained(*args, **kwargs)
+
     def forward(self, input_ids=None, labels=None, image_patches=None, image_patches_indices=None, attention_mask=None, position_ids=None,
-                past_key_values=None, inputs_embeds=None, use_cache=None, return_dict=True, **unused):
+                past_key_values=None, inputs_embeds=None, use_cache=None, return_dict=True, _last_position_only=False, **unused):
         if input_ids is not None and inputs_embeds is not None:
             raise ValueError("You cannot specify both decoder_input_ids and decoder_inputs_embeds at the same time")
         if input_ids is None and inputs_embeds is None:
@@ -513,5 +574,6 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
                 else:
                     pe = [w(p.to(w.weight.dtype)).squeeze(0) for p in image_patches]
                 inputs_embeds = self.gather_continuous_embeddings(inputs_embeds, pe, image_patches_indices)
+        kw = {"_last_position_only": True} if _last_position_only else {}
         return self.language_model(inputs_embeds=inputs_embeds, labels=labels, attention_mask=attention_mask, position_ids=position_ids,
-                                   past_key_values=past_key_values, use_cache=use_cache)
+                                   past_key_values=past_key_values, use_cache=use_cache, **kw)

@@ -829,8 +829,8 @@ def _w8_weight_ok(qweight, scale) -> bool:
 
 
 def gemv_w8(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfloat16, out=None):
-    """y [M, N] = (x [M, K] . qweight [N, K]^T) * scale [N] (+ bias) (then exact-erf GELU when act == 1), 1 <= M <= 16
-    (otter_gemv_w8, csrc/w8.hip).  x bf16 with unit column stride, qweight int8 (row stride % 16 == 0), scale fp32 [N], bias bf16 / fp32 [N]
+    """y [M, N] = (x [M, K] . qweight [N, K]^T) * scale [N] (+ bias), then `act` (0 none, 1 exact-erf GELU, 3 squared ReLU relu(v)^2 in
+    fp32; no other code), 1 <= M <= 16 (otter_gemv_w8, csrc/w8.hip).  x bf16 with unit column stride, qweight int8 (row stride % 16 == 0), scale fp32 [N], bias bf16 / fp32 [N]
     or None; y bf16 or fp32 (`out`: a caller-owned [M, N] view with unit column stride, written in place)."""
     K.require_cuda(x, qweight, scale, bias, out)
     if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
@@ -863,7 +863,7 @@ def gemm_w8_rows_workspace_bytes(M: int, N: int, K: int) -> int:
 
 
 def gemm_w8_rows(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfloat16, out=None):
-    """gemv_w8's product, arguments and rules for 1 <= M <= 64 (otter_gemm_w8_rows, csrc/w8.hip): the one-token steps of 17 to 64 rows.
+    """gemv_w8's product, arguments, `act` codes (0, 1, 3) and rules for 1 <= M <= 64 (otter_gemm_w8_rows, csrc/w8.hip): the one-token steps of 17 to 64 rows.
     Row m of the result has the same bits whatever M is and whatever the other rows of x hold."""
     K.require_cuda(x, qweight, scale, bias, out)
     if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:

@@ -4,6 +4,7 @@
 the step is a single pass over the weights.  Storing those weights as int8 with one fp32 scale per output row halves the bytes a step
 moves and the decoder's footprint; the activations stay bf16 and the accumulation fp32 (csrc/w8.hip).  This is an opt-in, in-memory
 transformation applied after loading (`OtterForConditionalGeneration.quantize_decoder_int8()`); nothing on the training path changes.
+The OtterHD / Fuyu host has the same method (`FuyuForCausalLM.quantize_decoder_int8()`): `quantize_persimmon_decoder`.
 
 Format.  For a weight W [N, K] read as fp32:
     amax[n]  = max_k |W[n, k]|
@@ -81,15 +82,19 @@ def release_scratch() -> None:
     _scratch.clear()
 
 
+_ACT_CODES = {None: 0, "gelu": 1, "relu2": 3}          # the `act` argument of otter_gemv_w8 / otter_gemm_w8_rows (include/otter_hip.h)
+
+
 class Int8FrozenLinear(nn.Module):
     """A frozen nn.Linear held as int8 weights + one fp32 scale per output row (buffers `qweight`, `scale`, `bias`).  Inference only.
 
-    forward(x, act=None) -- `act="gelu"` applies the exact-erf GELU to the output:
-      * GPU input of at most 16 rows (leading dimensions flattened): `ops.gemv_w8`, one pass over the int8 weight, scale / bias / GELU in
-        its epilogue.  x is cast to bf16 if it is not; the output has the compute dtype the unquantised layer would have produced.
+    forward(x, act=None) -- `act="gelu"` applies the exact-erf GELU to the output, `act="relu2"` the squared ReLU of the Persimmon MLP:
+      * GPU input of at most 16 rows (leading dimensions flattened): `ops.gemv_w8`, one pass over the int8 weight, scale / bias / activation
+        in its epilogue.  x is cast to bf16 if it is not; the output has the compute dtype the unquantised layer would have produced.
       * GPU input of 17 to 64 rows in a one-token step ([rows, 1, K]: batch x beams of a cached step): `ops.gemm_w8_rows`, the same
         single pass over the int8 weight (see `route`).
-      * Any other GPU input (prompt prefill, more than 64 rows): `ops.dequant_w8` into the process-wide bf16 scratch, then the library GEMM.
+      * Any other GPU input (prompt prefill, more than 64 rows): `ops.dequant_w8` into the process-wide bf16 scratch, then the library GEMM
+        (then the GELU / squared-ReLU kernel).
       * CPU input: F.linear(x, dequantize_weight_int8(...), bias).  The ONE deliberate exception to this package's "no CPU fallback"
         rule: the host contract (module swap, parity with the fake-quantised model, error paths) has to be testable without a GPU.  No
         product path runs the decoder on the CPU.
@@ -127,14 +132,14 @@ class Int8FrozenLinear(nn.Module):
         return self.qweight.numel() + 4 * self.scale.numel() + (self.bias.numel() * self.bias.element_size() if self.bias is not None else 0)
 
     def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
-        if act not in (None, "gelu"):
-            raise ValueError("Int8FrozenLinear: act must be None or 'gelu'")
+        if act not in _ACT_CODES:
+            raise ValueError("Int8FrozenLinear: act must be None, 'gelu' or 'relu2'")
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("the int8 decoder is inference-only: its input requires grad (run it under torch.no_grad(); training or LoRA "
                                "on quantised weights is not supported)")
         if not x.is_cuda:
             y = F.linear(x, dequantize_weight_int8(self.qweight, self.scale, x.dtype), None if self.bias is None else self.bias.to(x.dtype))
-            return F.gelu(y) if act else y
+            return F.gelu(y) if act == "gelu" else torch.square(F.relu(y)) if act == "relu2" else y
         cd = OF.compute_dtype_for(x)
         lead = x.shape[:-1]
         x2 = x.reshape(-1, self.in_features)
@@ -144,14 +149,16 @@ class Int8FrozenLinear(nn.Module):
             if xb.stride(1) != 1 or (xb.shape[0] > 1 and xb.stride(0) % 8) or xb.data_ptr() % 16:
                 xb = xb.contiguous()
             product = ops.gemv_w8 if how == "gemv" else ops.gemm_w8_rows
-            y = product(xb, self.qweight, self.scale, self.bias, 1 if act else 0, out_dtype=cd)
+            y = product(xb, self.qweight, self.scale, self.bias, _ACT_CODES[act], out_dtype=cd)
             return y.view(lead + (self.out_features,))
         n, k = self.qweight.shape
         w = ops.dequant_w8(self.qweight, self.scale, out=_dequant_scratch(n * k, x.device)[: n * k].view(n, k))
         with torch.autocast("cuda", enabled=False):
             y = F.linear(xb, w, None if self.bias is None else self.bias.to(torch.bfloat16))
-        if act:
+        if act == "gelu":
             y = OF.gelu(y)
+        elif act == "relu2":
+            y = ops.sqrelu_fwd(y)
         return (y if cd == torch.bfloat16 else y.to(cd)).view(lead + (self.out_features,))
 
 
@@ -201,4 +208,42 @@ def quantize_frozen_decoder(lang_encoder: nn.Module) -> dict:
                     if f is not None and hasattr(f, "mods"):
                         f.release()
                         f.mods = [swapped.get(id(m), m) for m in f.mods]     # (or the replaced weights stay alive; `usable()` is False for these)
+    return {"replaced": replaced, "bytes_before": before, "bytes_after": after}
+
+
+def quantize_persimmon_decoder(lm: nn.Module, lm_head: bool = True) -> dict:
+    """Replace `query_key_value`, `dense`, `dense_h_to_4h` and `dense_4h_to_h` of every PersimmonDecoderLayer of `lm` (a
+    fuyu.PersimmonForCausalLM) by an Int8FrozenLinear, and with `lm_head` the untied un-embedding too.  Left alone: `embed_tokens`, every
+    LayerNorm (q_layernorm / k_layernorm included) and whatever lives outside `lm` (Fuyu's vision_embed_tokens).  The OtterHD recipe
+    fine-tunes the whole model, so these are ordinary trainable nn.Linear: the call is the user's statement that training is over and
+    they are quantised whatever their requires_grad is (`Int8FrozenLinear.from_linear` keeps refusing trainable layers; this goes through
+    `quantize_weight_int8` and the constructor).  Returns {"replaced", "bytes_before", "bytes_after"}; a second call replaces nothing."""
+    from .fuyu import PersimmonDecoderLayer
+
+    replaced, before, after = 0, 0, 0
+
+    def swap(parent, name):
+        nonlocal replaced, before, after
+        child = getattr(parent, name)
+        if type(child) is not nn.Linear or child.in_features % 16:
+            return
+        q, s = quantize_weight_int8(child.weight)
+        new = Int8FrozenLinear(q, s, None if child.bias is None else child.bias.detach())
+        before += child.weight.numel() * child.weight.element_size()
+        before += child.bias.numel() * child.bias.element_size() if child.bias is not None else 0
+        after += new.nbytes()
+        for store in (OF.shadows._w, OF.shadows._wt):           # the compute-dtype copies a training run left of the replaced weight
+            for key in [k for k in store if k[0] == id(child.weight)]:
+                del store[key]
+        setattr(parent, name, new)
+        replaced += 1
+
+    for layer in list(lm.modules()):
+        if isinstance(layer, PersimmonDecoderLayer):
+            swap(layer.self_attn, "query_key_value")
+            swap(layer.self_attn, "dense")
+            swap(layer.mlp, "dense_h_to_4h")
+            swap(layer.mlp, "dense_4h_to_h")
+    if lm_head:
+        swap(lm, "lm_head")
     return {"replaced": replaced, "bytes_before": before, "bytes_after": after}
