@@ -366,6 +366,53 @@ int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const flo
                                 float eps, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_persimmon_decode_attn_cached / otter_persimmon_decode_attn_cached_dyn -- otter_persimmon_decode_attn over a STATIC key / value
+ * cache (otter_amd/kv_cache.py), head_dim 64: the new key / value of each of the N rows (batch x beams, all at position `pos`) are written
+ * in place into slot [n, h, pos] of a preallocated cache, and the row's single query attends over keys 0..pos -- keys before `pos` read
+ * through a beam indirection table.  Nothing of the past is copied.
+ *   qkv      [N, H, 3, 64] bf16 contiguous, 16-byte aligned: q | k | v of the new token per head (the projection output, read in place)
+ *   gamma_q / beta_q / gamma_k / beta_k  fp32 [64]
+ *   cos_row / sin_row  (scalar entry) fp32 [rot]: the rotary table row of position pos.
+ *   cos_table / sin_table  (dyn entry) fp32 [>= S_max, rot] with a row stride >= rot (elements): the kernel takes row pos itself.
+ *   k_cache / v_cache  bf16, indexed [row, h, key, 64]: row and head strides in elements (multiples of 8, head stride >= S_max * 64),
+ *            key stride 64, 16-byte aligned, capacity S_max keys.  Only slot [n, :, pos, :] of each row n is written: the normalised +
+ *            rotated k rounded to bf16 once, and the raw v.
+ *   src      int32 [N, >= pos] (dyn: [N, >= S_max - 1]) with a row stride, or NULL: src[n, t] = the cache row holding sequence n's
+ *            key / value at position t < pos (NULL: the row's own).  Entries outside [0, N) are clamped into it.
+ *   key_valid  uint8 [N, >= pos + 1] (dyn: [N, >= S_max]) with a row stride (0 = padded key), or NULL.  A row with every key masked gives
+ *            o = 0.
+ *   o        bf16 [N, H * 64] contiguous (the input of `dense`).
+ *   workspace  fp32 scratch of at least OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES(N, H, pos + 1) bytes (dyn:
+ *            OTTER_PERSIMMON_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max)).
+ *   pos_dev  (dyn entry) const int32 [1] in device memory, 4-byte aligned: read by the kernel.  A value outside [1, S_max) makes the
+ *            call a no-op (o and the cache are left untouched): a corrupt counter never indexes the cache.
+ * head_dim 64 only; rot a multiple of 16 in (0, 64]; 1 <= pos < S_max <= 65536.  The arithmetic, the key ranges and the order of every
+ * reduction are those of otter_persimmon_decode_attn: on the same inputs (the past being the gathered cache, B = N, S_past = pos) o and
+ * the written key slot are bit-identical to its o and k_new[:, :, S_past].  No workgroup reads a slot this call writes (reads: keys
+ * < pos; writes: slot pos of the own row; key pos is taken from the new token itself), which is what makes the in-place update safe.
+ * The dyn entry's launch (grid, workspace size, scalar arguments) does not depend on the position, so one captured launch can be replayed
+ * at every position of a generate() call: its grid covers the most key ranges any position below S_max can have, a workgroup whose range
+ * is not live returns before it touches memory, and the live ranges are combined in range order -- at every pos its o and cache slot are
+ * bit-identical to the scalar entry's.  It validates before it launches, allocates nothing, does not synchronise, and queries the
+ * device only for its CU count, once per device (call it once outside a stream capture).
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES(N, H, Sk) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(Sk) + 127) / 128) * 66 * 4)
+int otter_persimmon_decode_attn_cached(const void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
+                                       const float* cos_row, const float* sin_row, void* k_cache, int64_t k_cache_row_stride,
+                                       int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride, int64_t v_cache_head_stride,
+                                       const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride, void* o,
+                                       void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim,
+                                       int64_t rot, float eps, float scale, void* stream);
+#define OTTER_PERSIMMON_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(S_max) + 127) / 128) * 66 * 4)
+int otter_persimmon_decode_attn_cached_dyn(const void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
+                                           const float* cos_table, const float* sin_table, int64_t table_row_stride, void* k_cache,
+                                           int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                           int64_t v_cache_head_stride, const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid,
+                                           int64_t key_valid_row_stride, void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H,
+                                           const int32_t* pos_dev, int64_t S_max, int64_t head_dim, int64_t rot, float eps, float scale,
+                                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * otter_decode_attn_cached -- one cached decode step over a STATIC key / value cache (otter_amd/kv_cache.py), head_dim 128: the new
  * key / value of each of the N rows (batch x beams, all at position `pos`) are written in place into slot [n, h, pos] of a
  * preallocated cache, and the row's single query attends over keys 0..pos -- keys before `pos` read through a beam indirection table.

@@ -134,6 +134,10 @@ SIGNATURES = {
                                  _i64, _f32, _vp]),
     "otter_persimmon_decode_attn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                            _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
+    "otter_persimmon_decode_attn_cached": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                                  _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp]),
+    "otter_persimmon_decode_attn_cached_dyn": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64,
+                                                      _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _f32, _f32, _vp]),
     "otter_decode_attn_cached": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64,
                                         _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp]),
     "otter_decode_attn_cached_dyn": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp,

@@ -24,6 +24,10 @@ bf16 GPU path (every parameter is trainable here, so the GEMMs are torch / hipBL
   cached decode step (S = 1, no grad)    csrc/persimmon_decode.hip: otter_persimmon_decode_attn -- q/k LayerNorm + rotary of the new token,
                                          the cache append (one read of the past, one write of the new cache) and the single-query
                                          attention in one pass; OTTER_FUYU_HIP_DECODE=0 keeps the plain path (A/B switch)
+  the same step over a StaticKVCache     csrc/persimmon_decode_cache.hip: otter_persimmon_decode_attn_cached (/ _dyn in replay mode) -- the
+  (`generate(past_key_values=cache)`)    same arithmetic, the new key / value written in place at the row's own slot, the past never
+                                         moved, beams through the cache's int32 table; with `graph_decode=True` one captured step is
+                                         replayed (otter_amd/graph_decode.py).  OTTER_FUYU_HIP_DECODE=0: the plain-torch restatement
 fp32 / CPU: the plain PyTorch expression of the same arithmetic (parity mode; pinned by tests/golden/fuyu_tiny.npz, generated
 by the reference's own FuyuForCausalLM)."""
 from __future__ import annotations
@@ -41,6 +45,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from . import functional as OF
 from . import ops
+from .kv_cache import StaticKVCache, cache_geometry
 
 
 def _rotate_half(x):
@@ -72,6 +77,73 @@ def _refuse_save_if_int8(model):
     if quant is not None and any(isinstance(m, quant.Int8FrozenLinear) for m in model.modules()):
         raise RuntimeError("save_pretrained: the decoder of this model was quantised in memory (quantize_decoder_int8); its state_dict is "
                            "not a reference-format checkpoint.  Save the model before quantising it.")
+
+
+def _check_static_cache_kind(cache, who: str) -> None:
+    if cache.int8:
+        raise NotImplementedError("%s: an int8 StaticKVCache (kv_dtype='int8') is not built for the Persimmon host (head_dim 64)" % who)
+
+
+def _same_device(a, b) -> bool:
+    a, b = torch.device(a), torch.device(b)
+    if a.type != b.type:
+        return False
+    return a.type != "cuda" or (torch.cuda.current_device() if a.index is None else a.index) == (torch.cuda.current_device() if b.index is None
+                                                                                                  else b.index)
+
+
+def _pop_static_cache(who: str, generate_kwargs: dict, config, emb, rows: int, prompt_len: int):
+    """`generate(..., past_key_values=cache)`: pop and check a caller's StaticKVCache (None when none was given; anything else stays in
+    the arguments and is refused as ever).  `config`: the Persimmon config; `rows` = batch x beams."""
+    from .generation import resolve_max_length
+
+    cache = generate_kwargs.get("past_key_values")
+    if not isinstance(cache, StaticKVCache):
+        return None
+    del generate_kwargs["past_key_values"]
+    _check_static_cache_kind(cache, who)
+    if cache.length != 0:
+        raise ValueError("%s: the StaticKVCache holds %d positions; pass an empty one (cache.reset())" % (who, cache.length))
+    cd = OF.compute_dtype_for(emb)
+    if not _same_device(cache.device, emb.device) or cache.dtype != cd:
+        raise ValueError("%s: the StaticKVCache is on %s in %s, the model computes on %s in %s" % (who, cache.device, cache.dtype, emb.device, cd))
+    n_layers, n_kv, head_dim, host_max = cache_geometry(config)
+    if (cache.n_layers, cache.n_heads, cache.head_dim) != (n_layers, n_kv, head_dim):
+        raise ValueError("%s: the StaticKVCache has %d layers of %d heads x %d, the model %d of %d x %d (StaticKVCache.for_model)"
+                         % (who, cache.n_layers, cache.n_heads, cache.head_dim, n_layers, n_kv, head_dim))
+    if cache.rows != rows:
+        raise ValueError("%s: the StaticKVCache has %d rows, this call needs batch x num_beams = %d" % (who, cache.rows, rows))
+    need = min(resolve_max_length(prompt_len, generate_kwargs.get("max_new_tokens"), generate_kwargs.get("max_length")), host_max)
+    if cache.max_len < need:
+        raise ValueError("%s: the StaticKVCache holds at most %d positions, this call can reach %d" % (who, cache.max_len, need))
+    return cache
+
+
+def _static_cache_step(model, lm, cache, num_beams: int, graph_decode: bool, graph_step: list, prompt_kw: dict, kw: dict):
+    """The step closure of `generate(past_key_values=cache)` (OtterForConditionalGeneration.generate's static branch): the prompt pass goes
+    through `model` with `prompt_kw` (the image patches) and fills the cache; on a beam step the cache's table is reordered, not the
+    cache; later steps feed the last token.  `graph_decode`: after the prompt pass the cache enters replay mode and the steps go through
+    one GraphDecodeStep (kept in `graph_step[0]` for the caller's `finally`)."""
+    from .graph_decode import GraphDecodeStep
+
+    def cached(ids):
+        return model(input_ids=ids, past_key_values=cache, use_cache=True, **kw).logits[:, -1, :]
+
+    def step(ids, mask, past, beam_idx):
+        if past is None:                                # rows = sentences x beams: generate_tokens has repeated the prompt already
+            out = model(input_ids=ids, attention_mask=mask, past_key_values=cache, use_cache=True, **prompt_kw, **kw)
+            return out.logits[:, -1, :], cache
+        if beam_idx is not None:
+            cache.reorder(beam_idx)                     # the table moves, the cache does not
+        if graph_decode:
+            if graph_step[0] is None:
+                cache.enable_replay(mask[:, :cache.length] if mask is not None else None, beams=num_beams > 1)
+                graph_step[0] = GraphDecodeStep(lm, cache, None, step_fn=cached, kernel_head_dim=64)
+            return graph_step[0](ids[:, -1:]), cache
+        out = model(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=cache, use_cache=True, **kw)
+        return out.logits[:, -1, :], cache
+
+    return step
 
 
 class PersimmonMLP(nn.Module):
@@ -139,6 +211,24 @@ class PersimmonAttention(nn.Module):
                                             past_key_value[1], key_valid, self.rot, self.q_layernorm.eps, self.scale)
         return _linear(self.dense, o.view(B, 1, self.hidden)), ((k, v) if use_cache else None)
 
+    def static_step(self, x, cos, sin, cache, layer: int, key_valid, reference: bool = False):
+        """Cached decode step over a StaticKVCache (x [B,1,D], no autograd): the projection, then `cache.attend_persimmon` -- q/k LayerNorm +
+        rotary at the cache's position, the in-place append and the single-query attention, on csrc/persimmon_decode_cache.hip where the
+        cache's kernel conditions hold, the plain-torch restatement elsewhere (and with `reference`) -- then `dense`.  cos / sin: the rows of
+        the position, or in replay mode the whole tables."""
+        B = x.shape[0]
+        qkv = _linear(self.query_key_value, x).view(B, self.n_heads, 3, self.head_dim)
+        if not self.qk_layernorm:
+            ln, reference = (None, None, None, None), True          # (the kernel fuses the LayerNorm: without one, the restatement)
+        elif qkv.is_cuda and qkv.dtype == torch.bfloat16:
+            ln = self._ln_f32()
+        else:
+            ln = (self.q_layernorm.weight, self.q_layernorm.bias, self.k_layernorm.weight, self.k_layernorm.bias)
+        fn = cache.attend_persimmon_reference if reference else cache.attend_persimmon
+        eps = self.q_layernorm.eps if self.qk_layernorm else 0.0
+        o = fn(layer, qkv, ln[0], ln[1], ln[2], ln[3], cos, sin, self.rot, eps, self.scale, key_valid=key_valid)
+        return _linear(self.dense, o.view(B, 1, self.hidden))
+
     def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False, key_valid=None):
         B, S, _ = x.shape
         H, d = self.n_heads, self.head_dim
@@ -182,18 +272,21 @@ class PersimmonDecoderLayer(nn.Module):
         self.post_attention_layernorm = nn.LayerNorm(config.hidden_size, eps=config.layer_norm_eps)
 
     def forward(self, x, cos, sin, attn_mask=None, past_key_value=None, use_cache=False, hip=False, pending=None, defer=False, key_valid=None,
-                decode=None):
+                decode=None, static=None):
         """hip path: `pending` is the previous layer's MLP output, not yet added to the residual stream -- the add rides in this layer's
         first LayerNorm pass; with `defer` the layer hands its own MLP output back the same way ((x, past, mlp_out) instead of (x, past)).
         `key_valid`: uint8 [B,S] key-padding mask of a left-padded prompt (inference only); `decode` = (cos_row, sin_row): the cached
-        one-token step on csrc/persimmon_decode.hip against `past_key_value` (key_valid then [B,S_past+1])."""
+        one-token step on csrc/persimmon_decode.hip against `past_key_value` (key_valid then [B,S_past+1]).  `static` = (cache, layer index,
+        reference): the one-token step over a StaticKVCache (`PersimmonAttention.static_step`), on either path; cos / sin as it takes them."""
         if hip:
             n1, n2 = self.input_layernorm, self.post_attention_layernorm
             if pending is not None:
                 x, a = OF.add_layer_norm(x, pending, n1.weight, n1.bias, n1.eps, torch.bfloat16)   # x = x + pending ; a = LN(x)  (one pass)
             else:
                 a = OF.layer_norm(x, n1.weight, n1.bias, n1.eps, torch.bfloat16)
-            if decode is not None:
+            if static is not None:
+                b, new_past = self.self_attn.static_step(a, cos, sin, static[0], static[1], key_valid, static[2]), None
+            elif decode is not None:
                 b, new_past = self.self_attn.decode_step(a, decode[0], decode[1], past_key_value, key_valid, use_cache)
             else:
                 b, new_past = self.self_attn(a, cos, sin, use_cache=use_cache, hip=True, key_valid=key_valid)
@@ -201,7 +294,10 @@ class PersimmonDecoderLayer(nn.Module):
             if defer:
                 return x, new_past, self.mlp(m)
             return x + self.mlp(m), new_past
-        b, new_past = self.self_attn(self.input_layernorm(x), cos, sin, attn_mask=attn_mask, past_key_value=past_key_value, use_cache=use_cache)
+        if static is not None:
+            b, new_past = self.self_attn.static_step(self.input_layernorm(x), cos, sin, static[0], static[1], key_valid, static[2]), None
+        else:
+            b, new_past = self.self_attn(self.input_layernorm(x), cos, sin, attn_mask=attn_mask, past_key_value=past_key_value, use_cache=use_cache)
         x = x + b
         return x + self.mlp(self.post_attention_layernorm(x)), new_past
 
@@ -280,6 +376,15 @@ class PersimmonModel(PersimmonPreTrainedModel):
         x = self.embed_tokens(input_ids) if inputs_embeds is None else inputs_embeds
         B, S = x.shape[:2]
         s_past = 0
+        # a StaticKVCache (otter_amd/kv_cache.py) as `past_key_values`: empty, the ordinary prompt pass below fills it; after that a
+        # one-token step appends in place (`_static_step`).  The object itself is returned as the new cache.
+        cache = past_key_values if isinstance(past_key_values, StaticKVCache) else None
+        if cache is not None:
+            _check_static_cache_kind(cache, "PersimmonModel.forward")
+            cache.check_step(B, S)
+            if cache.length > 0:
+                return self._static_step(x, cache, attention_mask, position_ids)
+            past_key_values, use_cache = None, True
         if past_key_values is not None and len(past_key_values) and past_key_values[0] is not None and len(past_key_values[0]) == 2:
             s_past = past_key_values[0][0].shape[2]
         s_k = S + s_past
@@ -331,14 +436,68 @@ class PersimmonModel(PersimmonPreTrainedModel):
                                          key_valid=key_valid, decode=dec)
             else:
                 x, npkv = layer(x, cos, sin, attn_mask=mask, past_key_value=pkv, use_cache=use_cache)
-            if use_cache:
+            if cache is not None:
+                cache.fill(i, npkv[0], npkv[1])      # one strided copy each, from the views the pass returns
+            elif use_cache:
                 new_pasts.append(npkv)
+        if cache is not None:
+            cache.length = S
         n = self.final_layernorm
         if pending is not None:
             x = OF.add_layer_norm(x, pending, n.weight, n.bias, n.eps, OF.compute_dtype_for(x))[1]
         else:
             x = OF.layer_norm(x, n.weight, n.bias, n.eps, OF.compute_dtype_for(x)) if x.is_cuda else n(x)
+        if cache is not None:
+            return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
         return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=tuple(new_pasts) if use_cache else None)
+
+    def _static_step(self, x, cache, attention_mask, position_ids):
+        """The one-token step over a non-empty StaticKVCache: per layer the projection, `cache.attend_persimmon` and `dense`; the position
+        moves once, after the last layer.  On the GPU in bf16 the layer runs its fused LayerNorm passes as the default cache's HIP step
+        does, so that the two give the same logits; OTTER_FUYU_HIP_DECODE=0 sends the attention to the plain-torch restatement.
+        Replay mode (`cache.enable_replay`): nothing here may depend on the position on the host side -- `attention_mask` and
+        `position_ids` must be None (the mask is the cache's own), and the rotary tables are built to the cache's capacity before the first
+        such step and must not move afterwards."""
+        s_past = cache.length
+        key_valid = None
+        if cache.replay:
+            if attention_mask is not None or position_ids is not None:
+                raise ValueError("PersimmonModel.forward: a StaticKVCache in replay mode takes attention_mask=None and position_ids=None "
+                                 "(the mask is the cache's own `valid`, the position its `pos_dev`)")
+            tabs = getattr(cache, "rotary_tables", None)
+            if tabs is None:                        # the first replay-mode step: built to the capacity, the address is fixed from here on
+                tabs = cache.rotary_tables = self._tables(cache.max_len, x.device)
+            elif self._tab is None or self._tab[0] is not tabs[0]:
+                raise RuntimeError("PersimmonModel.forward: the rotary tables were rebuilt while a StaticKVCache is in replay mode (a longer "
+                                   "forward ran in between): a captured step reads them at a fixed address")
+            cos, sin = tabs
+        else:
+            if position_ids is not None and not (position_ids.shape[0] == 1 and position_ids.shape[1] == 1 and int(position_ids[0, 0]) == s_past):
+                raise ValueError("PersimmonModel.forward: a step over a StaticKVCache takes the default positions (position_ids=None)")
+            cos_t, sin_t = self._tables(s_past + 1, x.device)
+            cos, sin = cos_t[s_past], sin_t[s_past]
+            if attention_mask is not None:
+                am = attention_mask.bool()
+                if not bool(am.all()):
+                    key_valid = am[:, -(s_past + 1):].to(torch.uint8).contiguous()
+        hip = x.is_cuda and OF.compute_dtype_for(x) == torch.bfloat16 and os.environ.get("OTTER_NO_FLASH") != "1"
+        reference = os.environ.get("OTTER_FUYU_HIP_DECODE", "1") == "0"
+        pending = None
+        for i, layer in enumerate(self.layers):
+            if hip:
+                x, _, pending = layer(x, cos, sin, hip=True, pending=pending, defer=True, key_valid=key_valid, static=(cache, i, reference))
+            else:
+                x, _ = layer(x, cos, sin, key_valid=key_valid, static=(cache, i, reference))
+        if cache.replay:
+            cache.advance()
+        else:
+            cache.length += 1
+        n = self.final_layernorm
+        if pending is not None:
+            x = OF.add_layer_norm(x, pending, n.weight, n.bias, n.eps, OF.compute_dtype_for(x))[1]
+        else:
+            x = OF.layer_norm(x, n.weight, n.bias, n.eps, OF.compute_dtype_for(x)) if x.is_cuda else n(x)
+        return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
 
 
 class PersimmonForCausalLM(PersimmonPreTrainedModel):
@@ -391,6 +550,17 @@ class PersimmonForCausalLM(PersimmonPreTrainedModel):
                                       "Persimmon host (head_dim 64)")
 
         kw = {"_last_position_only": True} if _is_int8(self.lm_head) else {}
+        nb = int(generate_kwargs.get("num_beams", 1) or 1)
+        cache = _pop_static_cache("PersimmonForCausalLM.generate", generate_kwargs, self.config, self.model.embed_tokens.weight,
+                                  input_ids.shape[0] * nb, input_ids.shape[1])
+        if cache is not None:           # a caller's StaticKVCache (implies use_cache); `graph_decode=True` only together with one
+            graph_step = [None]
+            step = _static_cache_step(self, self, cache, nb, bool(generate_kwargs.pop("graph_decode", False)), graph_step, {}, kw)
+            try:
+                return generate_tokens(step, input_ids, attention_mask, **generate_kwargs)
+            finally:
+                if graph_step[0] is not None:
+                    graph_step[0].release()
 
         def step(ids, mask, past, beam_idx):
             if use_cache and past is not None:
@@ -514,20 +684,34 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
         cache_impl = generate_kwargs.pop("cache_implementation", None)
         if cache_impl == "static":
             raise NotImplementedError("FuyuForCausalLM.generate: cache_implementation='static' is not built for the Persimmon host (head_dim 64, "
-                                      "fused q/k LayerNorm + partial rotary): use the default cache, whose step runs on csrc/persimmon_decode.hip")
+                                      "fused q/k LayerNorm + partial rotary): use the default cache, whose step runs on csrc/persimmon_decode.hip, or pass a "
+                                      "cache object: past_key_values=StaticKVCache.for_model(model, rows, max_len)")
         if cache_impl not in (None, "dynamic"):
             raise ValueError("generate: cache_implementation must be None, 'dynamic' or 'static', got %r" % (cache_impl,))
-        if generate_kwargs.pop("graph_decode", False):
-            raise NotImplementedError("FuyuForCausalLM.generate: graph_decode=True replays a step over the static cache, which is not built "
-                                      "for the Persimmon host")
         L0 = input_ids.shape[1]
         nb = int(generate_kwargs.get("num_beams", 1) or 1)
+        cache = _pop_static_cache("FuyuForCausalLM.generate", generate_kwargs, self.config.text_config,
+                                  self.language_model.model.embed_tokens.weight, input_ids.shape[0] * nb, L0)
+        graph_decode = bool(generate_kwargs.pop("graph_decode", False))
+        if graph_decode and cache is None:
+            raise NotImplementedError("FuyuForCausalLM.generate: graph_decode=True replays a step over the static cache, which is not built "
+                                      "for the Persimmon host (what is built takes a cache object: past_key_values=StaticKVCache.for_model("
+                                      "model, rows, max_len), with graph_decode=True beside it)")
         patches, idx0 = image_patches, image_patches_indices
         if nb > 1 and patches is not None:          # every beam of a sample sees that sample's image
             patches = (patches.repeat_interleave(nb, dim=0) if torch.is_tensor(patches) else [p for p in patches for _ in range(nb)])
             idx0 = idx0.repeat_interleave(nb, dim=0)
 
         kw = {"_last_position_only": True} if _is_int8(self.language_model.lm_head) else {}
+        if cache is not None:           # a caller's StaticKVCache (implies use_cache): the prompt pass, with the patches, fills it
+            graph_step = [None]
+            step = _static_cache_step(self, self.language_model, cache, nb, graph_decode, graph_step,
+                                      {"image_patches": patches, "image_patches_indices": idx0}, kw)
+            try:
+                return generate_tokens(step, input_ids, attention_mask, **generate_kwargs)
+            finally:
+                if graph_step[0] is not None:
+                    graph_step[0].release()
 
         def step(ids, mask, past, beam_idx):
             if use_cache and past is not None:
@@ -563,7 +747,8 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
             raise ValueError("You have to specify either decoder_input_ids or decoder_inputs_embeds")
         if inputs_embeds is None:
             inputs_embeds = self.language_model.get_input_embeddings()(input_ids)
-            if image_patches is not None and past_key_values is None:
+            if image_patches is not None and (past_key_values is None or (isinstance(past_key_values, StaticKVCache)
+                                                                          and past_key_values.length == 0)):
                 w = self.vision_embed_tokens
                 if torch.is_tensor(image_patches):
                     pe = list(w(image_patches.to(w.weight.dtype)))                  # one GEMM for the whole batch

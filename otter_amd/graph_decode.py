@@ -47,20 +47,27 @@ def _capture_stream(device) -> "torch.cuda.Stream":
 class GraphDecodeStep:
     """The cached steps of one `generate` call.  `lm` is the decoder host (MPT / LLaMA with the Otter mixin), `cache` a prefilled
     StaticKVCache in replay mode, `media` the filled MediaCache.  Call it with the new ids [rows, 1]; it returns the logits [rows, vocab] of
-    that step (from the third step on: the graph's static output buffer, valid until the next call)."""
+    that step (from the third step on: the graph's static output buffer, valid until the next call).
 
-    def __init__(self, lm, cache, media):
+    A host without a media cache (OtterHD / Fuyu-8B: otter_amd/fuyu.py) passes `media=None` and its own `step_fn(ids [rows, 1]) -> logits
+    [rows, vocab]`, one replay-mode step over `cache`; `kernel_head_dim` is the head size at which that host's cached step runs on a HIP
+    kernel (128: csrc/decode_cache.hip; 64: csrc/persimmon_decode_cache.hip)."""
+
+    def __init__(self, lm, cache, media, step_fn=None, kernel_head_dim: int = 128):
         if not cache.replay:
             raise ValueError("GraphDecodeStep: the StaticKVCache must be in replay mode (enable_replay)")
         self.lm, self.cache, self.media = lm, cache, media
-        media.fixed_address = True
+        if step_fn is not None:
+            self._eager = step_fn
+        if media is not None:
+            media.fixed_address = True
         self.steps = self.captures = self.replays = 0
         self.capture_seconds = 0.0
         self.graph = self.logits = self.ids = self.stream = None
         # the graph needs every layer's step to be the HIP kernel's (StaticKVCache.uses_kernel: the plain-torch restatement reads the
         # position back to the host).  What the cache alone decides is decided here; the rest of that predicate (the query's dtype,
         # grouped key / value heads) is known after the warm-up steps, which the cache reports as `kernel_steps`.
-        self.use_graph = cache.k.is_cuda and cache.dtype == torch.bfloat16 and cache.head_dim == 128
+        self.use_graph = cache.k.is_cuda and cache.dtype == torch.bfloat16 and cache.head_dim == kernel_head_dim
         if self.use_graph:
             self.ids = torch.zeros((cache.rows, 1), dtype=torch.long, device=cache.device)
             self.stream = _capture_stream(cache.device)

@@ -48,6 +48,13 @@ invariant above carries over.  `fill` quantises the prompt with torch ops; a cac
 attends to it in its dequantised form, so a step returns what "append, then attend over the cache" returns.  `dtype` stays the compute
 dtype (what `attend` and `to_legacy` return in).  The kernel conditions are those of the unquantised cache (`uses_kernel`); everywhere
 else `attend_reference` runs its int8 branch.
+
+The OtterHD / Fuyu-8B (Persimmon) host (otter_amd/fuyu.py: head_dim 64, q / k LayerNorm per head and a partial rotary embedding fused into the
+step) takes the cache as an object: `StaticKVCache.for_model(model, rows, max_len)` passed to `generate` as `past_key_values`, `reset()`
+between calls.  Its step is `attend_persimmon`: csrc/persimmon_decode_cache.hip (`ops.persimmon_decode_attn_cached`, `_dyn` in replay
+mode) on the GPU in bf16 -- the arithmetic of csrc/persimmon_decode.hip line for line, so the static cache returns the default cache's
+tokens there -- and `attend_persimmon_reference` everywhere else.  The layout, the table, replay mode and the in-place invariant are the
+ones above; an int8 cache at head_dim 64 is not built (`NotImplementedError`).
 """
 from __future__ import annotations
 
@@ -62,7 +69,10 @@ def rotate_half(x: torch.Tensor) -> torch.Tensor:
 
 
 def cache_geometry(config):
-    """(n_layers, key / value heads, head_dim, the host's position limit) of a decoder host's config (MPT or LLaMA)."""
+    """(n_layers, key / value heads, head_dim, the host's position limit) of a decoder host's config (MPT, LLaMA or Persimmon; a FuyuConfig
+    stands for its `text_config`)."""
+    if getattr(config, "model_type", None) == "fuyu":
+        config = config.text_config
     if hasattr(config, "d_model"):          # MPTConfig
         return int(config.n_layers), int(config.n_heads), int(config.d_model) // int(config.n_heads), int(config.max_seq_len)
     heads = int(config.num_attention_heads)
@@ -149,6 +159,31 @@ class StaticKVCache:
         if self.length + S > self.max_len:
             raise ValueError("StaticKVCache: %d + %d positions exceed max_len=%d" % (self.length, S, self.max_len))
 
+    @classmethod
+    def for_model(cls, model_or_config, rows: int, max_len: int, device=None, dtype=None, kv_dtype: Optional[str] = None) -> "StaticKVCache":
+        """A cache of the geometry of a decoder host (`cache_geometry` of its config), for a caller who passes the cache to `generate` as
+        `past_key_values` (the OtterHD / Fuyu host).  `model_or_config`: a model or its config; `device` / `dtype` default to the model's
+        embedding's device and compute dtype (a config alone: the CPU and fp32)."""
+        config = getattr(model_or_config, "config", model_or_config)
+        n_layers, n_kv, head_dim, _ = cache_geometry(config)
+        if device is None or dtype is None:
+            emb = model_or_config.get_input_embeddings().weight if hasattr(model_or_config, "get_input_embeddings") else None
+            if device is None:
+                device = emb.device if emb is not None else torch.device("cpu")
+            if dtype is None:
+                dtype = emb.dtype if emb is not None and emb.dtype in (torch.bfloat16, torch.float64) else torch.float32
+        return cls(n_layers, rows, n_kv, head_dim, max_len, device, dtype, kv_dtype=kv_dtype)
+
+    def reset(self) -> None:
+        """Make the cache empty again for the next `generate` call: no positions, no beam table, replay mode left.  The buffers stay as
+        they are: nothing beyond `length` is ever read."""
+        self.length = 0
+        self.src = None
+        self.pos_dev = None
+        self.valid = None
+        self.kernel_steps = True
+        self.rotary_tables = None       # (the Persimmon host keeps the tables a replay-mode step reads here: otter_amd/fuyu.py)
+
     def fill(self, layer: int, k: torch.Tensor, v: torch.Tensor) -> None:
         """Prefill: k, v indexed [rows, n_heads, S, head_dim] (any strides: the views the flash and SDPA paths produce) -> positions [0, S).
         One strided copy per tensor.  int8: the prompt's vectors are rounded to the compute dtype first, so that the quantiser sees what
@@ -230,10 +265,10 @@ class StaticKVCache:
 
     def to_legacy(self, host) -> tuple:
         """The tuple-of-tuples cache in the host's own layout, gathered through the table: "mpt" (or an MPT module) k [N,H,d,S], v [N,H,S,d];
-        "llama" k, v [N,H,S,d].  int8: dequantised, in the compute dtype."""
+        "llama" and "persimmon" (also a Persimmon / Fuyu module) k, v [N,H,S,d].  int8: dequantised, in the compute dtype."""
         name = host if isinstance(host, str) else type(host).__name__
         mpt = "mpt" in name.lower()
-        if not mpt and "llama" not in name.lower():
+        if not mpt and not any(h in name.lower() for h in ("llama", "persimmon", "fuyu")):
             raise ValueError("StaticKVCache.to_legacy: host must be 'mpt' or 'llama' (or one of their modules), got %r" % (name,))
         out = []
         for i in range(self.n_layers):
@@ -332,3 +367,79 @@ class StaticKVCache:
         if dead is not None:
             o = o.masked_fill(dead[:, None, None], 0.0)
         return o.reshape(N, H * d).to(q.dtype)
+
+    # ---- the cached step of the Persimmon host (OtterHD / Fuyu-8B): q / k LayerNorm per head + partial rotary fused into the step ---------
+
+    def uses_persimmon_kernel(self, qkv: torch.Tensor, rot: int) -> bool:
+        return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and self.dtype == torch.bfloat16 and not self.int8 and self.head_dim == 64
+                and rot % 16 == 0 and 0 < rot <= 64)
+
+    def attend_persimmon(self, layer: int, qkv, gq, bq, gk, bk, cos, sin, rot: int, eps: float, scale: float, key_valid=None) -> torch.Tensor:
+        """One cached step of `layer` of the Persimmon host at position `length` (which the caller advances once per forward, after the last
+        layer): qkv [N,H,3,d] the projection of the new token (per head q | k | v); gq / bq / gk / bk fp32 [d] the q / k LayerNorm's gamma
+        and beta; cos / sin fp32 [rot] rows of that position; key_valid uint8 / bool [N, length+1] or None.  Returns o [N, H*d] in qkv's
+        dtype.  Replay mode: the position is `pos_dev`, cos / sin are the whole fp32 tables [>= max_len, rot] and the mask is the cache's
+        own `valid` (key_valid must be None).  On csrc/persimmon_decode_cache.hip where `uses_persimmon_kernel` holds, everywhere else the
+        plain-torch restatement."""
+        if self.int8:
+            raise NotImplementedError("StaticKVCache.attend_persimmon: an int8 key / value cache is not built for head_dim 64 (the Persimmon host)")
+        if self.replay and key_valid is not None:
+            raise ValueError("StaticKVCache.attend_persimmon: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
+        if self.uses_persimmon_kernel(qkv, rot):
+            from . import ops
+
+            if self.replay:
+                return ops.persimmon_decode_attn_cached_dyn(qkv, gq, bq, gk, bk, cos, sin, self.k[layer], self.v[layer], self.pos_dev, rot, eps,
+                                                            scale, src=self.src, key_valid=self.valid)
+            return ops.persimmon_decode_attn_cached(qkv, gq, bq, gk, bk, cos, sin, self.k[layer], self.v[layer], self.length, rot, eps, scale,
+                                                    src=self.src, key_valid=key_valid)
+        return self.attend_persimmon_reference(layer, qkv, gq, bq, gk, bk, cos, sin, rot, eps, scale, key_valid=key_valid)
+
+    def attend_persimmon_reference(self, layer: int, qkv, gq, bq, gk, bk, cos, sin, rot: int, eps: float, scale: float,
+                                   key_valid=None) -> torch.Tensor:
+        """What csrc/persimmon_decode_cache.hip does, in plain torch on any device and dtype: LayerNorm of q and k over the head and the
+        rotate-half rotary on their first `rot` dims in fp32 at least (fp64 for fp64 inputs), k rounded to the cache dtype once, k and the raw
+        v appended at slot `length` of the row's own row, keys 0..length gathered through the table, padding mask, softmax in fp32 at
+        least, a fully masked row -> 0.  Replay mode: the position is read from `pos_dev` (not from `length`), cos / sin are the whole
+        tables, of which row `pos` is taken, the mask is columns 0..pos of `valid`, and `kernel_steps` is cleared (this step reads the
+        position back to the host: it cannot be captured).  The same deliberate exception to "no PyTorch path" as `attend_reference`."""
+        if self.int8:
+            raise NotImplementedError("StaticKVCache.attend_persimmon: an int8 key / value cache is not built for head_dim 64 (the Persimmon host)")
+        pos, N, H, d = self.length, qkv.shape[0], qkv.shape[1], qkv.shape[3]
+        if self.replay:
+            self.kernel_steps = False
+            pos = int(self.pos_dev.item())
+            if key_valid is not None:
+                raise ValueError("StaticKVCache.attend_persimmon_reference: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
+            key_valid = self.valid
+            if cos.dim() != 2 or cos.shape[0] < self.max_len:
+                raise ValueError("StaticKVCache: replay mode takes the whole cos / sin tables [>= max_len, rot]")
+            if 0 <= pos < cos.shape[0]:
+                cos, sin = cos[pos], sin[pos]
+        if pos < 1 or pos >= self.max_len:
+            raise ValueError("StaticKVCache: a cached step needs 1 <= length < max_len (length=%d, max_len=%d)" % (pos, self.max_len))
+        ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+        qf, kf, v_new = qkv[:, :, 0].to(ct), qkv[:, :, 1].to(ct), qkv[:, :, 2]
+        if gq is not None:
+            qf = torch.nn.functional.layer_norm(qf, (d,), gq.to(ct), bq.to(ct), eps)
+            kf = torch.nn.functional.layer_norm(kf, (d,), gk.to(ct), bk.to(ct), eps)
+        c, s = cos.to(ct).view(1, 1, rot), sin.to(ct).view(1, 1, rot)
+        qf = torch.cat((qf[..., :rot] * c + rotate_half(qf[..., :rot]) * s, qf[..., rot:]), dim=-1)
+        kf = torch.cat((kf[..., :rot] * c + rotate_half(kf[..., :rot]) * s, kf[..., rot:]), dim=-1)
+        qf = qf.to(qkv.dtype).to(ct)                                           # (the kernel rounds q' to the compute dtype, then scales)
+        self.k[layer, :, :, pos] = kf.to(self.dtype)
+        self.v[layer, :, :, pos] = v_new.to(self.dtype)
+        k = self._gathered(self.k[layer], pos + 1).to(ct)                      # column pos of the table is the row's own index
+        v = self._gathered(self.v[layer], pos + 1).to(ct)
+        s_ = torch.einsum("nhd,nhjd->nhj", qf * scale, k)
+        dead = None
+        if key_valid is not None:
+            ok = key_valid[:, :pos + 1].bool()
+            s_ = s_.masked_fill(~ok[:, None, :], float("-inf"))
+            dead = ~ok.any(dim=1)
+            if bool(dead.any()):
+                s_ = s_.masked_fill(dead[:, None, None], 0.0)
+        o = torch.einsum("nhj,nhjd->nhd", torch.softmax(s_, dim=-1), v)
+        if dead is not None:
+            o = o.masked_fill(dead[:, None, None], 0.0)
+        return o.reshape(N, H * d).to(qkv.dtype)

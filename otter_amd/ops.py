@@ -543,7 +543,104 @@ def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past,
     return o, k_new, v_new
 
 
-DECODE_CACHED_MAX_KEYS = 65536         # include/otter_hip.h: S_max <= 65536
+def persimmon_decode_cached_workspace_bytes(N: int, H: int, Sk: int) -> int:
+    """OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES of include/otter_hip.h."""
+    return N * H * ((Sk + 127) // 128) * 66 * 4
+
+
+def persimmon_decode_cached_dyn_workspace_bytes(N: int, H: int, S_max: int) -> int:
+    """OTTER_PERSIMMON_DECODE_CACHED_DYN_WORKSPACE_BYTES of include/otter_hip.h."""
+    return N * H * ((S_max + 127) // 128) * 66 * 4
+
+
+def _persimmon_cached_common(name, qkv, gq, bq, gk, bk, k_cache, v_cache, rot):
+    """The checks the two static-cache entry points share; returns (N, H, S_max)."""
+    if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[2:] != (3, 64) or not qkv.is_contiguous() or qkv.data_ptr() % 16:
+        raise K.OtterHipError(f"{name}: qkv must be contiguous bf16 [N,H,3,64], 16-B aligned")
+    N, H = qkv.shape[:2]
+    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
+    for t in (k_cache, v_cache):
+        if (t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 64) or t.stride(3) != 1 or t.stride(2) != 64
+                or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < S_max * 64 or t.data_ptr() % 16):
+            raise K.OtterHipError(f"{name}: k_cache / v_cache must be bf16 [N,H,S_max,64] with key stride 64, unit dim stride, 16-B aligned")
+    if S_max < 2 or S_max > PERSIMMON_DECODE_MAX_KEYS:
+        raise K.OtterHipError(f"{name}: S_max={S_max} outside [2, {PERSIMMON_DECODE_MAX_KEYS}]")
+    for t in (gq, bq, gk, bk):
+        if t.dtype != torch.float32 or t.numel() != 64 or not t.is_contiguous():
+            raise K.OtterHipError(f"{name}: gamma / beta must be contiguous fp32 [64]")
+    if rot <= 0 or rot > 64 or rot % 16:
+        raise K.OtterHipError(f"{name}: rot={rot} must be a multiple of 16 in (0, 64]")
+    return N, H, S_max
+
+
+def persimmon_decode_attn_cached(qkv, gq, bq, gk, bk, cos_row, sin_row, k_cache, v_cache, pos, rot, eps, scale, src=None, key_valid=None):
+    """One cached Persimmon decode step over a static cache (otter_persimmon_decode_attn_cached).  qkv [N,H,3,64] bf16 contiguous; gq / bq /
+    gk / bk fp32 [64]; cos_row / sin_row fp32 [rot] (position `pos`); k_cache / v_cache bf16 [N,H,S_max,64] with key stride 64, written in
+    place at slot `pos` (1 <= pos < S_max) of every row; src int32 [N, >= pos] (row stride free) or None; key_valid uint8 [N, >= pos+1] or
+    None.  Returns o [N,H*64] bf16."""
+    K.require_cuda(qkv, gq, bq, gk, bk, cos_row, sin_row, k_cache, v_cache, src, key_valid)
+    N, H, S_max = _persimmon_cached_common("persimmon_decode_attn_cached", qkv, gq, bq, gk, bk, k_cache, v_cache, rot)
+    pos = int(pos)
+    if pos < 1 or pos >= S_max:
+        raise K.OtterHipError(f"persimmon_decode_attn_cached: pos={pos} outside [1, S_max) with S_max={S_max}")
+    for t in (cos_row, sin_row):
+        if t.dtype != torch.float32 or t.numel() != rot or not t.is_contiguous():
+            raise K.OtterHipError("persimmon_decode_attn_cached: cos_row / sin_row must be contiguous fp32 [rot]")
+    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < pos or src.stride(1) != 1
+                            or (N > 1 and src.stride(0) < pos)):
+        raise K.OtterHipError("persimmon_decode_attn_cached: src must be int32 [N, >= pos] with a unit column stride")
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < pos + 1
+                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < pos + 1)):
+        raise K.OtterHipError("persimmon_decode_attn_cached: key_valid must be uint8 [N, >= pos+1] with a unit column stride")
+    o = torch.empty((N, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    ws = _ws.get(persimmon_decode_cached_workspace_bytes(N, H, pos + 1), qkv.device)
+    K.check(K.lib().otter_persimmon_decode_attn_cached(
+        qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_row.data_ptr(), sin_row.data_ptr(), k_cache.data_ptr(),
+        k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), K.ptr(src),
+        max(src.stride(0), pos) if src is not None else 0, K.ptr(key_valid), max(key_valid.stride(0), pos + 1) if key_valid is not None else 0,
+        o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 64, int(rot), float(eps), float(scale), K.stream()),
+        "persimmon_decode_attn_cached")
+    return o
+
+
+def persimmon_decode_attn_cached_dyn(qkv, gq, bq, gk, bk, cos_table, sin_table, k_cache, v_cache, pos_dev, rot, eps, scale, src=None,
+                                     key_valid=None, out=None):
+    """persimmon_decode_attn_cached with the position in device memory (otter_persimmon_decode_attn_cached_dyn): pos_dev int32 [1] on the
+    device, read by the kernel (a value outside [1, S_max) makes the call a no-op); cos_table / sin_table fp32 [>= S_max, rot] (the kernel
+    takes row pos); src int32 [N, >= S_max - 1]; key_valid uint8 [N, >= S_max].  No argument of the launch depends on the position: the same
+    call, captured in a graph, serves every step.  Returns o [N,H*64] bf16 (`out`: a contiguous bf16 [N,H*64] tensor to write instead)."""
+    K.require_cuda(qkv, gq, bq, gk, bk, cos_table, sin_table, k_cache, v_cache, pos_dev, src, key_valid, out)
+    N, H, S_max = _persimmon_cached_common("persimmon_decode_attn_cached_dyn", qkv, gq, bq, gk, bk, k_cache, v_cache, rot)
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
+        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: pos_dev must be an int32 tensor of one element")
+    for t in (cos_table, sin_table):
+        if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != rot or t.stride(1) != 1 or t.stride(0) < rot
+                or t.stride() != cos_table.stride()):
+            raise K.OtterHipError("persimmon_decode_attn_cached_dyn: cos_table / sin_table must be fp32 [>= S_max, rot] with a unit dim stride "
+                                  "and equal strides")
+    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < S_max - 1 or src.stride(1) != 1
+                            or (N > 1 and src.stride(0) < S_max - 1)):
+        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: src must be int32 [N, >= S_max - 1] with a unit column stride")
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < S_max
+                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < S_max)):
+        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: key_valid must be uint8 [N, >= S_max] with a unit column stride")
+    if out is None:
+        o = torch.empty((N, H * 64), dtype=torch.bfloat16, device=qkv.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * 64) or not out.is_contiguous():
+        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: out must be a contiguous bf16 [N, H*64] tensor")
+    else:
+        o = out
+    ws = _ws.get(persimmon_decode_cached_dyn_workspace_bytes(N, H, S_max), qkv.device)
+    K.check(K.lib().otter_persimmon_decode_attn_cached_dyn(
+        qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(),
+        cos_table.stride(0), k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1),
+        K.ptr(src), max(src.stride(0), S_max - 1) if src is not None else 0, K.ptr(key_valid),
+        max(key_valid.stride(0), S_max) if key_valid is not None else 0, o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos_dev.data_ptr(),
+        S_max, 64, int(rot), float(eps), float(scale), K.stream()), "persimmon_decode_attn_cached_dyn")
+    return o
+
+
+DECODE_CACHED_MAX_KEYS = 65536        # include/otter_hip.h: S_max <= 65536
 
 
 def decode_attn_cached_workspace_bytes(N: int, H: int, Sk: int) -> int:
