@@ -13,21 +13,15 @@
 // The new token is attended in its DEQUANTISED form (codes and scale from LDS), so a step returns what "append, then attend over the cache"
 // returns.
 //
-// Shape: grid (key range, head, row), 256 threads.  A cached vector is 128 bytes, so an 8-lane group owns one key at a time (lane l8: dims
+// Shape: the split-key step of csrc/decode_split.h.  A cached vector is 128 bytes, so an 8-lane group owns one key at a time (lane l8: dims
 // 16 l8 .. 16 l8 + 15, one 16-byte load each of K and V codes; the key's two scales are one 4-byte load each, the same address in all 8 lanes),
 // 32 groups, two keys per group in flight = 64 keys per iteration: s = k_scale * sum q[i] code_k[i] by an 8-lane butterfly, online softmax per
-// group, acc += (p * v_scale) * code_v[i].  The 32 groups are combined through LDS in a fixed order; with more than one range each workgroup
-// writes (m, l, o[128]) to the workspace and a second kernel combines the ranges in range order.
-//
-// The split rule is decode_cache.hip's with this kernel's 64 keys per iteration (that file is left byte for byte as it was, so the few lines
-// of the rule are restated here rather than moved).
-#include "common.h"
+// group, acc += (p * v_scale) * code_v[i].
+#include "decode_split.h"
 
 namespace {
 
-constexpr int HD = 128, NT = 256, LANES = 8, GROUPS = NT / LANES, UNROLL = 2, KEYS_PER_ITER = GROUPS * UNROLL, DPL = HD / LANES;
-constexpr int MIN_KEYS_PER_SPLIT = 128, PART = 2 + HD;   // workspace record per (row, head, range): m, l, o[128]
-constexpr int64_t S_MAX_LIMIT = 65536;
+constexpr int HD = 128, LANES = 8, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL, DPL = HD / LANES;
 
 struct DqArgs {
     const bf16_t* q; int64_t q_rs, q_hs;                  // new token: q / k / v [n, h, 128], row / head strides (elements), dim stride 1
@@ -47,39 +41,6 @@ struct DqArgs {
     float scale;
 };
 
-// THE SPLIT RULE of decode_cache.hip (both entry points, host and device): about two workgroups per CU over all (row, head, range), at least
-// MIN_KEYS_PER_SPLIT keys per range, a multiple of KEYS_PER_ITER keys each.  The range count is not monotone in Sk, so the dyn grid is sized by
-// dq_max_ranges, the bound, not by the count at the capacity.
-struct DqSplit { int kps, nsplit; };
-
-__host__ __device__ inline int64_t dq_want(int64_t NH, int cus) {
-    const int64_t want = (2 * (int64_t)cus + NH - 1) / NH;
-    return want > 0 ? want : 1;
-}
-
-__host__ __device__ inline DqSplit dq_split(int64_t Sk, int64_t NH, int cus) {
-    const int64_t want = dq_want(NH, cus);
-    int64_t kps = (Sk + want - 1) / want;
-    if (kps < MIN_KEYS_PER_SPLIT) kps = MIN_KEYS_PER_SPLIT;
-    kps = (kps + KEYS_PER_ITER - 1) / KEYS_PER_ITER * KEYS_PER_ITER;
-    DqSplit s;
-    s.kps = (int)kps;
-    s.nsplit = (int)((Sk + kps - 1) / kps);
-    return s;
-}
-
-__host__ __device__ inline int64_t dq_max_ranges(int64_t S_max, int64_t NH, int cus) {
-    const int64_t want = dq_want(NH, cus), by_keys = (S_max + MIN_KEYS_PER_SPLIT - 1) / MIN_KEYS_PER_SPLIT;
-    return want < by_keys ? want : by_keys;
-}
-
-__device__ __forceinline__ float group8_sum(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
 // 16 int8 codes -> 16 floats (exact)
 __device__ __forceinline__ void unpack16(const uint4& r, float (&v)[DPL]) {
     const uint32_t w[4] = {r.x, r.y, r.z, r.w};
@@ -90,32 +51,12 @@ __device__ __forceinline__ void unpack16(const uint4& r, float (&v)[DPL]) {
     }
 }
 
-// double -> bf16 in ONE rounding (decode_cache.hip)
-__device__ __forceinline__ bf16_t d2bf(double y) {
-    float f = (float)y;
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0xffffu) == 0x8000u) {
-        const double r = y - (double)f;
-        if (r != 0.0) f = __uint_as_float((r > 0.0) == (f > 0.f) ? u + 1 : u - 1);
-    }
-    return f2bf(f);
-}
-
-// element d of the (optionally rotated) vector x[0..127]: x[d] c[d] + rotate_half(x)[d] s[d], rotate_half(x) = (-x[64..127], x[0..63])
-__device__ __forceinline__ double rotated(const bf16_t* x, const float* cs, const float* sn, int d) {
-    const double xd = (double)bf2f(x[d]);
-    if (!cs) return xd;
-    const double xp = (double)bf2f(x[d ^ 64]);
-    return xd * (double)cs[d] + (d < 64 ? -xp : xp) * (double)sn[d];
-}
-
 // one workgroup's share of a step: range `split` of row blockIdx.z, head blockIdx.y
 __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int split, const int pos, const int nsplit, const int kps,
                                                       const float* cs_tab, const float* sn_tab) {
     __shared__ float qs[HD];                                        // scale * q'
     __shared__ __attribute__((aligned(16))) int8_t code_new[2][HD]; // the new token's codes: [0] k', [1] v
     __shared__ float scale_new[2], wave_amax[NT / OTTER_WAVE];
-    __shared__ float red_m[GROUPS], red_l[GROUPS], red_o[GROUPS][HD];
     const int h = blockIdx.y, n = blockIdx.z, tid = threadIdx.x;
     const int64_t nh = (int64_t)n * a.H + h;
 
@@ -207,10 +148,10 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < DPL; ++i) s = fmaf(q[i], k[i], s);
-            s = group8_sum(s);                            // (all lanes: the shuffles stay convergent)
+            s = group_sum<LANES>(s);                      // (all lanes: the shuffles stay convergent)
             s = fmaf(s, ksc[u], slope * (float)(j - pos));
             if (!live || (kv && kv[j] == 0)) s = -INFINITY;
-            const float mn = fmaxf(m, s);
+            const float mn = fmaxf(m, s);                 // (softmax_update of decode_split.h, with the value scale; see there)
             if (mn != -INFINITY) {
                 const float alpha = __expf(m - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
                 const float pv = p * vsc[u];
@@ -222,7 +163,8 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
         }
     }
 
-    // 4. the 32 groups, in order
+    // 4. the 32 groups, in order (combine_groups of decode_split.h; see there)
+    __shared__ float red_m[GROUPS], red_l[GROUPS], red_o[GROUPS][HD];
     if (l8 == 0) { red_m[g] = m; red_l[g] = l; }
 #pragma unroll
     for (int i = 0; i < DPL; ++i) red_o[g][DPL * l8 + i] = acc[i];
@@ -241,7 +183,7 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
         if (nsplit == 1) {
             a.o[nh * HD + tid] = f2bf(L > 0.f ? O / L : 0.f);
         } else {
-            float* pr = a.part + (nh * a.part_stride + split) * PART;
+            float* pr = a.part + (nh * a.part_stride + split) * PART<HD>;
             if (tid < 2) pr[tid] = tid == 0 ? M : L;
             pr[2 + tid] = O;
         }
@@ -252,35 +194,15 @@ __global__ __launch_bounds__(NT) void decode_cached_i8_kernel(DqArgs a) {
     decode_cached_i8_body(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
 }
 
-// nsplit > 1: one workgroup of 128 lanes per (head, row) combines the ranges in range order; p = the (row, head)'s first record
-__device__ __forceinline__ void decode_cached_i8_combine_body(const float* __restrict__ p, bf16_t* __restrict__ o, int64_t nh, int nsplit) {
-    const int d = threadIdx.x;
-    float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[s * PART]);
-    float L = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-        for (int s = 0; s < nsplit; ++s) {
-            const float ms = p[s * PART];
-            const float f = ms == -INFINITY ? 0.f : __expf(ms - M);
-            L = fmaf(p[s * PART + 1], f, L);
-            O = fmaf(p[s * PART + 2 + d], f, O);
-        }
-    }
-    o[nh * HD + d] = f2bf(L > 0.f ? O / L : 0.f);
-}
-
 __global__ __launch_bounds__(HD) void decode_cached_i8_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
     const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    decode_cached_i8_combine_body(part + nh * nsplit * PART, o, nh, nsplit);
+    combine_ranges<HD>(part, o, nh, nsplit, nsplit);
 }
 
-// ---- the position in device memory (decode_cache.hip): grid (max_ranges, H, N) for the capacity; a workgroup whose range is not live at the
-// current position, or any workgroup when the position is outside [1, S_max), returns before it touches memory or reaches a barrier --------
+// ---- the position in device memory (decode_split.h): grid (max_ranges, H, N) for the capacity --------------------------------------------
 __global__ __launch_bounds__(NT) void decode_cached_i8_dyn_kernel(DqArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus,
                                                                   int64_t table_rs) {
-    const int pos = *pos_dev;
-    if (pos < 1 || pos >= S_max) return;
-    const DqSplit sp = dq_split((int64_t)pos + 1, (int64_t)a.N * a.H, cus);
+    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)a.N * a.H, cus);
     if ((int)blockIdx.x >= sp.nsplit) return;
     // row `pos` of the rotary tables, shared by every row (cs_rs = 0)
     decode_cached_i8_body(a, blockIdx.x, pos, sp.nsplit, sp.kps, a.cs ? a.cs + (int64_t)pos * table_rs : nullptr,
@@ -290,23 +212,11 @@ __global__ __launch_bounds__(NT) void decode_cached_i8_dyn_kernel(DqArgs a, cons
 __global__ __launch_bounds__(HD) void decode_cached_i8_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
                                                                           const int32_t* __restrict__ pos_dev, int N, int H, int S_max, int cus,
                                                                           int max_ranges) {
-    const int pos = *pos_dev;
-    if (pos < 1 || pos >= S_max) return;
-    const int nsplit = min(dq_split((int64_t)pos + 1, (int64_t)N * H, cus).nsplit, max_ranges);
+    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)N * H, cus);
+    const int nsplit = min(sp.nsplit, max_ranges);
     if (nsplit == 1) return;                              // the one live workgroup wrote o itself
     const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    decode_cached_i8_combine_body(part + nh * max_ranges * PART, o, nh, nsplit);
-}
-
-int cu_count() {
-    static int counts[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (counts[dev] == 0) {
-        int n = 0;
-        counts[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return counts[dev];
+    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
 }
 
 bool mult(int64_t m, int64_t a, int64_t b) { return a % m == 0 && b % m == 0; }
@@ -364,7 +274,7 @@ int otter_decode_attn_cached_i8(const void* q, int64_t q_row_stride, int64_t q_h
     const int64_t need = OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES(N, H, Sk);
     OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_i8: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
 
-    const DqSplit sp = dq_split(Sk, N * H, cu_count());
+    const Split sp = split_rule<KEYS_PER_ITER>(Sk, N * H, cu_count());
     const int64_t nsplit = sp.nsplit;
 
     DqArgs a;
@@ -403,9 +313,8 @@ int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t
     const int64_t need = OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES(N, H, S_max);
     OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_i8_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
 
-    // the CU count is looked up once per device (a step that is to be captured has run eagerly before: no device query under capture)
     const int cus = cu_count();
-    const int64_t max_ranges = dq_max_ranges(S_max, N * H, cus);
+    const int64_t max_ranges = split_max_ranges(S_max, N * H, cus);
 
     DqArgs a;
     DQ_FILL_ARGS(a);
@@ -424,3 +333,6 @@ int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t
 }
 
 }  // extern "C"
+
+#undef DQ_REQUIRE_COMMON
+#undef DQ_FILL_ARGS

@@ -4,21 +4,16 @@
 // cache and one write of the new one.  bf16 storage, fp32 arithmetic (the rotate-half convention and the LayerNorm of
 // fuyu.hip's qk_norm_rope_fwd_kernel).
 //
-// Grid (split, head, batch), 256 threads.  Every workgroup normalises and rotates q (and k) of its (batch, head) itself (128 elements:
-// cheaper than a launch); the keys of a (batch, head) are cut into `nsplit` contiguous ranges of `kps` keys (flash-decoding), sized so
-// that B * H * nsplit is about two workgroups per CU of the device the call runs on, with at least 128 keys per range.
-// Inside a workgroup an 8-lane group owns one key at a time (lane l8: dims 8 l8 .. 8 l8 + 7, one 16-byte load each of K and V), two
-// keys per group in flight: score by an 8-lane butterfly, online softmax per group (running max m, sum l, o[8]), and the K / V row
-// stored to the new cache from the same registers.  The 32 groups are combined through LDS in a fixed order; with nsplit > 1 each
-// workgroup writes (m, l, o[64]) to the workspace and a second kernel combines the ranges, again in a fixed order: deterministic.
+// Grid (split, head, batch), 256 threads, the split-key step of csrc/decode_split.h: every workgroup normalises and rotates q (and k) of its
+// (batch, head) itself (persimmon_new_token, 128 elements: cheaper than a launch); the keys of a (batch, head) are cut into `nsplit`
+// contiguous ranges of `kps` keys by split_rule.  An 8-lane group owns one key at a time (lane l8: dims 8 l8 .. 8 l8 + 7, one 16-byte
+// load each of K and V), two keys per group in flight, and stores the K / V row to the new cache from the same registers.
 // Masked keys (key_valid == 0) add nothing; a fully masked row gives o = 0, as csrc/decode.hip.
-#include "common.h"
+#include "decode_split.h"
 
 namespace {
 
-constexpr int HD = 64, NT = 256, GROUPS = NT / 8, UNROLL = 2, KEYS_PER_ITER = GROUPS * UNROLL;
-constexpr int MIN_KEYS_PER_SPLIT = 128, PART = 2 + HD;   // workspace record per (batch, head, range): m, l, o[64]
-constexpr int64_t SK_MAX = 65536;
+constexpr int HD = 64, LANES = 8, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL;
 
 struct PdArgs {
     const bf16_t* qkv;                                    // [B, H, 3, 64] contiguous: q | k | v of the new token, per head
@@ -33,48 +28,14 @@ struct PdArgs {
     float eps, scale;
 };
 
-__device__ __forceinline__ float group8_sum(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
-__device__ __forceinline__ void unpack8(const uint4& r, float (&v)[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-
 __global__ __launch_bounds__(NT) void persimmon_decode_kernel(PdArgs a) {
     __shared__ float qs[HD];                              // scale * bf16(q')
     __shared__ __attribute__((aligned(16))) bf16_t kv_new[2][HD];   // bf16(k') and v of the new token
-    __shared__ float red_m[GROUPS], red_l[GROUPS], red_o[GROUPS][HD];
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
     const int64_t bh = (int64_t)b * a.H + h;
 
-    // 1. wave w < 3 owns vector w of the new token (q, k, v), one element per lane
-    const int w = tid >> 6, lane = tid & 63;
-    if (w < 3) {
-        float x = bf2f(a.qkv[(bh * 3 + w) * HD + lane]);
-        if (w < 2) {
-            const float mean = wave_sum(x) * (1.0f / HD);
-            const float dx = x - mean;
-            const float rstd = rsqrtf(wave_sum(dx * dx) * (1.0f / HD) + a.eps);
-            x = dx * rstd * (w ? a.gk : a.gq)[lane] + (w ? a.bk : a.bq)[lane];
-            // rotate-half on the first `rot` dims: y1 = x1 c - x2 s, y2 = x2 c + x1 s
-            const int half = a.rot >> 1;
-            const bool in_rot = lane < a.rot, first = lane < half;
-            const float xp = __shfl(x, in_rot ? (first ? lane + half : lane - half) : lane, 64);
-            if (in_rot) x = x * a.cs[lane] + (first ? -xp : xp) * a.sn[lane];
-        }
-        const bf16_t xb = f2bf(x);
-        if (w == 0) qs[lane] = bf2f(xb) * a.scale;
-        else kv_new[w - 1][lane] = xb;
-    }
+    // 1. the new token
+    persimmon_new_token(a.qkv, bh, a.gq, a.bq, a.gk, a.bk, a.cs, a.sn, a.rot, a.eps, a.scale, qs, kv_new);
     __syncthreads();
 
     // 2. the workgroup's key range: scores, online softmax, P V, and the copy into the new cache
@@ -119,73 +80,36 @@ __global__ __launch_bounds__(NT) void persimmon_decode_kernel(PdArgs a) {
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) s = fmaf(q[i], k[i], s);
-            s = group8_sum(s);                            // (all lanes: the shuffles stay convergent)
+            s = group_sum<LANES>(s);                      // (all lanes: the shuffles stay convergent)
             if (!live || (kv && kv[j] == 0)) s = -INFINITY;
-            const float mn = fmaxf(m, s);
-            if (mn != -INFINITY) {
-                const float alpha = __expf(m - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
-                l = fmaf(l, alpha, p);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = fmaf(acc[i], alpha, p * v[i]);
-                m = mn;
-            }
+            const Softmax r = softmax_update(m, l, acc, s, v);
+            m = r.m;
+            l = r.l;
         }
     }
 
     // 3. the 32 groups, in order
-    if (l8 == 0) { red_m[g] = m; red_l[g] = l; }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) red_o[g][8 * l8 + i] = acc[i];
-    __syncthreads();
-    if (tid < HD) {
-        float M = -INFINITY;
-        for (int gg = 0; gg < GROUPS; ++gg) M = fmaxf(M, red_m[gg]);
-        float L = 0.f, O = 0.f;
-        if (M != -INFINITY) {
-            for (int gg = 0; gg < GROUPS; ++gg) {
-                const float f = red_m[gg] == -INFINITY ? 0.f : __expf(red_m[gg] - M);
-                L = fmaf(red_l[gg], f, L);
-                O = fmaf(red_o[gg][tid], f, O);
-            }
-        }
-        if (a.nsplit == 1) {
-            a.o[bh * HD + tid] = f2bf(L > 0.f ? O / L : 0.f);
-        } else {
-            float* pr = a.part + (bh * a.nsplit + split) * PART;
-            if (tid < 2) pr[tid] = tid == 0 ? M : L;
-            pr[2 + tid] = O;
-        }
-    }
+    combine_groups<HD, GROUPS>(g, 8 * l8, m, l, acc, a.o, a.part, bh, bh * a.nsplit + split, a.nsplit);
 }
 
-// nsplit > 1: one workgroup of 64 lanes per (head, batch) combines the ranges in order
+// nsplit > 1: one workgroup of 64 lanes per (head, batch) combines the ranges in order.  The statements of combine_ranges, written out: this
+// kernel never had them behind a function, and called through one its compiled branch condition has its two operands the other way round.
 __global__ __launch_bounds__(64) void persimmon_decode_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
     const int64_t bh = (int64_t)blockIdx.y * H + blockIdx.x;
     const int d = threadIdx.x;
-    const float* p = part + bh * nsplit * PART;
+    const float* p = part + bh * nsplit * PART<HD>;
     float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[s * PART]);
+    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[s * PART<HD>]);
     float L = 0.f, O = 0.f;
     if (M != -INFINITY) {
         for (int s = 0; s < nsplit; ++s) {
-            const float ms = p[s * PART];
+            const float ms = p[s * PART<HD>];
             const float f = ms == -INFINITY ? 0.f : __expf(ms - M);
-            L = fmaf(p[s * PART + 1], f, L);
-            O = fmaf(p[s * PART + 2 + d], f, O);
+            L = fmaf(p[s * PART<HD> + 1], f, L);
+            O = fmaf(p[s * PART<HD> + 2 + d], f, O);
         }
     }
     o[bh * HD + d] = f2bf(L > 0.f ? O / L : 0.f);
-}
-
-int cu_count() {
-    static int counts[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (counts[dev] == 0) {
-        int n = 0;
-        counts[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return counts[dev];
 }
 
 }  // namespace
@@ -204,7 +128,7 @@ int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const flo
     OTTER_REQUIRE(B > 0 && H > 0 && S_past > 0 && B <= 65535 && H <= 65535, "persimmon_decode_attn: bad shape B=%ld H=%ld S_past=%ld", (long)B,
                   (long)H, (long)S_past);
     const int64_t Sk = S_past + 1;
-    OTTER_REQUIRE(Sk <= SK_MAX, "persimmon_decode_attn: S_past + 1 = %ld keys exceeds the limit (%ld)", (long)Sk, (long)SK_MAX);
+    OTTER_REQUIRE(Sk <= S_MAX_LIMIT, "persimmon_decode_attn: S_past + 1 = %ld keys exceeds the limit (%ld)", (long)Sk, (long)S_MAX_LIMIT);
     OTTER_REQUIRE(rot > 0 && rot <= HD && rot % 16 == 0, "persimmon_decode_attn: rot=%ld must be a multiple of 16 in (0, 64]", (long)rot);
     OTTER_REQUIRE(k_dim_stride == 1 && v_dim_stride == 1, "persimmon_decode_attn: k_past / v_past need a unit dim stride");
     OTTER_REQUIRE(k_batch_stride % 8 == 0 && k_head_stride % 8 == 0 && k_key_stride % 8 == 0 && v_batch_stride % 8 == 0 && v_head_stride % 8 == 0 &&
@@ -215,12 +139,8 @@ int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const flo
     const int64_t need = OTTER_PERSIMMON_DECODE_WORKSPACE_BYTES(B, H, Sk);
     OTTER_REQUIRE(workspace_bytes >= need, "persimmon_decode_attn: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
 
-    // split rule: about two workgroups per CU over all (batch, head, range), at least MIN_KEYS_PER_SPLIT keys per range
-    const int64_t want = cdiv64(2 * (int64_t)cu_count(), B * H);
-    int64_t kps = cdiv64(Sk, want > 0 ? want : 1);
-    if (kps < MIN_KEYS_PER_SPLIT) kps = MIN_KEYS_PER_SPLIT;
-    kps = cdiv64(kps, KEYS_PER_ITER) * KEYS_PER_ITER;
-    const int64_t nsplit = cdiv64(Sk, kps);
+    const Split sp = split_rule<KEYS_PER_ITER>(Sk, B * H, cu_count());
+    const int64_t nsplit = sp.nsplit;
 
     PdArgs a;
     a.qkv = (const bf16_t*)qkv;
@@ -229,7 +149,7 @@ int otter_persimmon_decode_attn(const void* qkv, const float* gamma_q, const flo
     a.vp = (const bf16_t*)v_past; a.v_bs = v_batch_stride; a.v_hs = v_head_stride; a.v_ss = v_key_stride;
     a.kvalid = key_valid;
     a.kn = (bf16_t*)k_new; a.vn = (bf16_t*)v_new; a.o = (bf16_t*)o; a.part = (float*)workspace;
-    a.H = (int)H; a.Sp = (int)S_past; a.Sk = (int)Sk; a.rot = (int)rot; a.nsplit = (int)nsplit; a.kps = (int)kps;
+    a.H = (int)H; a.Sp = (int)S_past; a.Sk = (int)Sk; a.rot = (int)rot; a.nsplit = (int)nsplit; a.kps = sp.kps;
     a.eps = eps; a.scale = scale;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(persimmon_decode_kernel, dim3((unsigned)nsplit, (unsigned)H, (unsigned)B), dim3(NT), 0, st, a);

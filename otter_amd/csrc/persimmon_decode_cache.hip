@@ -4,12 +4,10 @@
 // N rows (batch x beams, all at the same position) attends over keys 0..pos -- the keys before `pos` read through a beam indirection table
 // (src[n, t] = the cache row that holds sequence n's key / value at position t) instead of a physically reordered cache.
 //
-// THE ARITHMETIC IS THAT OF persimmon_decode_kernel, LINE FOR LINE: fp32 LayerNorm of q and k over the 64-wide head by wave sums, fp32
-// rotate-half on the first `rot` dims, ONE rounding to bf16; an 8-lane group owns one key at a time (lane l8: dims 8 l8 .. 8 l8 + 7, one
-// 16-byte load each of K and V), 32 groups, two keys per group in flight, online softmax per group, a fixed-order LDS combine of the groups
-// and, with more than one key range, a fixed-order combine of the ranges; the ranges come from the same split rule (MIN_KEYS_PER_SPLIT 128,
-// about two workgroups per CU).  NOT csrc/decode_cache.hip's fp64 one-rounding rotation: on the same inputs `o` and the stored k' are
-// bit-identical to otter_persimmon_decode_attn's `o` and k_new[:, :, S_past], so the static cache returns the tokens of the default cache.
+// THE ARITHMETIC IS THAT OF persimmon_decode_kernel: the new token by the same persimmon_new_token, the same 8-lane groups (lane l8: dims
+// 8 l8 .. 8 l8 + 7, one 16-byte load each of K and V), 32 groups, two keys per group in flight, and the online softmax, the combines and
+// the split rule of csrc/decode_split.h.  NOT csrc/decode_cache.hip's fp64 one-rounding rotation: on the same inputs `o` and the stored k'
+// are bit-identical to otter_persimmon_decode_attn's `o` and k_new[:, :, S_past], so the static cache returns the tokens of the default cache.
 //
 // THE INVARIANT THE IN-PLACE UPDATE RESTS ON (csrc/decode_cache.hip, unchanged): no workgroup reads a slot that this launch writes.  Row n
 // writes slot [n, :, pos, :] only (one workgroup per (n, h): the one whose key range contains `pos`); every read of the cache is of a key
@@ -20,15 +18,13 @@
 // Two entry points share every line of arithmetic (persimmon_cached_body).  otter_persimmon_decode_attn_cached takes `pos` as a scalar and
 // sizes its grid from it.  otter_persimmon_decode_attn_cached_dyn reads `pos` from device memory and launches a grid sized for the cache's
 // CAPACITY: nothing in its launch depends on the position, so a captured graph of it can be replayed step after step.  Both derive the key
-// ranges of a position from pc_split (host and device); a workgroup of the dyn grid whose range index is not live at the current position
+// ranges of a position from split_rule (host and device); a workgroup of the dyn grid whose range index is not live at the current position
 // returns before it touches memory, and the combine kernel merges exactly the live ranges -- at every position the two give the same bits.
-#include "common.h"
+#include "decode_split.h"
 
 namespace {
 
-constexpr int HD = 64, NT = 256, GROUPS = NT / 8, UNROLL = 2, KEYS_PER_ITER = GROUPS * UNROLL;
-constexpr int MIN_KEYS_PER_SPLIT = 128, PART = 2 + HD;   // workspace record per (row, head, range): m, l, o[64]
-constexpr int64_t S_MAX_LIMIT = 65536;
+constexpr int HD = 64, LANES = 8, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL;
 
 struct PcArgs {
     const bf16_t* qkv;                                    // [N, H, 3, 64] contiguous: q | k | v of the new token, per head
@@ -43,77 +39,16 @@ struct PcArgs {
     float eps, scale;
 };
 
-// THE SPLIT RULE (csrc/persimmon_decode.hip's, in the form of csrc/decode_cache.hip's dc_split; both entry points, host and device): about
-// two workgroups per CU over all (row, head, range), at least MIN_KEYS_PER_SPLIT keys per range, a multiple of KEYS_PER_ITER keys each.
-// nsplit <= min(want, ceil(Sk / MIN_KEYS_PER_SPLIT)) with want = ceil(2 cus / (N H)).  The range count is NOT monotone in Sk (rounding kps up
-// can drop a range), so a grid that must serve every position up to a capacity is sized by pc_max_ranges, that bound.
-struct PcSplit { int kps, nsplit; };
-
-__host__ __device__ inline int64_t pc_want(int64_t NH, int cus) {
-    const int64_t want = (2 * (int64_t)cus + NH - 1) / NH;
-    return want > 0 ? want : 1;
-}
-
-__host__ __device__ inline PcSplit pc_split(int64_t Sk, int64_t NH, int cus) {
-    const int64_t want = pc_want(NH, cus);
-    int64_t kps = (Sk + want - 1) / want;
-    if (kps < MIN_KEYS_PER_SPLIT) kps = MIN_KEYS_PER_SPLIT;
-    kps = (kps + KEYS_PER_ITER - 1) / KEYS_PER_ITER * KEYS_PER_ITER;
-    PcSplit s;
-    s.kps = (int)kps;
-    s.nsplit = (int)((Sk + kps - 1) / kps);
-    return s;
-}
-
-__host__ __device__ inline int64_t pc_max_ranges(int64_t S_max, int64_t NH, int cus) {
-    const int64_t want = pc_want(NH, cus), by_keys = (S_max + MIN_KEYS_PER_SPLIT - 1) / MIN_KEYS_PER_SPLIT;
-    return want < by_keys ? want : by_keys;
-}
-
-__device__ __forceinline__ float group8_sum(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
-__device__ __forceinline__ void unpack8(const uint4& r, float (&v)[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-
 // one workgroup's share of a step: range `split` of row blockIdx.z, head blockIdx.y; cs / sn = the rotary row of `pos`
 __device__ __forceinline__ void persimmon_cached_body(const PcArgs& a, const int split, const int pos, const int nsplit, const int kps,
                                                       const float* cs, const float* sn) {
     __shared__ float qs[HD];                              // scale * bf16(q')
     __shared__ __attribute__((aligned(16))) bf16_t kv_new[2][HD];   // bf16(k') and v of the new token
-    __shared__ float red_m[GROUPS], red_l[GROUPS], red_o[GROUPS][HD];
     const int h = blockIdx.y, n = blockIdx.z, tid = threadIdx.x;
     const int64_t nh = (int64_t)n * a.H + h;
 
-    // 1. wave w < 3 owns vector w of the new token (q, k, v), one element per lane
-    const int w = tid >> 6, lane = tid & 63;
-    if (w < 3) {
-        float x = bf2f(a.qkv[(nh * 3 + w) * HD + lane]);
-        if (w < 2) {
-            const float mean = wave_sum(x) * (1.0f / HD);
-            const float dx = x - mean;
-            const float rstd = rsqrtf(wave_sum(dx * dx) * (1.0f / HD) + a.eps);
-            x = dx * rstd * (w ? a.gk : a.gq)[lane] + (w ? a.bk : a.bq)[lane];
-            // rotate-half on the first `rot` dims: y1 = x1 c - x2 s, y2 = x2 c + x1 s
-            const int half = a.rot >> 1;
-            const bool in_rot = lane < a.rot, first = lane < half;
-            const float xp = __shfl(x, in_rot ? (first ? lane + half : lane - half) : lane, 64);
-            if (in_rot) x = x * cs[lane] + (first ? -xp : xp) * sn[lane];
-        }
-        const bf16_t xb = f2bf(x);
-        if (w == 0) qs[lane] = bf2f(xb) * a.scale;
-        else kv_new[w - 1][lane] = xb;
-    }
+    // 1. the new token
+    persimmon_new_token(a.qkv, nh, a.gq, a.bq, a.gk, a.bk, cs, sn, a.rot, a.eps, a.scale, qs, kv_new);
     __syncthreads();
 
     const int l8 = tid & 7, g = tid >> 3;
@@ -161,79 +96,30 @@ __device__ __forceinline__ void persimmon_cached_body(const PcArgs& a, const int
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) s = fmaf(q[i], k[i], s);
-            s = group8_sum(s);                            // (all lanes: the shuffles stay convergent)
+            s = group_sum<LANES>(s);                      // (all lanes: the shuffles stay convergent)
             if (!live || (kv && kv[j] == 0)) s = -INFINITY;
-            const float mn = fmaxf(m, s);
-            if (mn != -INFINITY) {
-                const float alpha = __expf(m - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
-                l = fmaf(l, alpha, p);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = fmaf(acc[i], alpha, p * v[i]);
-                m = mn;
-            }
+            const Softmax r = softmax_update(m, l, acc, s, v);
+            m = r.m;
+            l = r.l;
         }
     }
 
     // 4. the 32 groups, in order
-    if (l8 == 0) { red_m[g] = m; red_l[g] = l; }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) red_o[g][8 * l8 + i] = acc[i];
-    __syncthreads();
-    if (tid < HD) {
-        float M = -INFINITY;
-        for (int gg = 0; gg < GROUPS; ++gg) M = fmaxf(M, red_m[gg]);
-        float L = 0.f, O = 0.f;
-        if (M != -INFINITY) {
-            for (int gg = 0; gg < GROUPS; ++gg) {
-                const float f = red_m[gg] == -INFINITY ? 0.f : __expf(red_m[gg] - M);
-                L = fmaf(red_l[gg], f, L);
-                O = fmaf(red_o[gg][tid], f, O);
-            }
-        }
-        if (nsplit == 1) {
-            a.o[nh * HD + tid] = f2bf(L > 0.f ? O / L : 0.f);
-        } else {
-            float* pr = a.part + (nh * a.part_stride + split) * PART;
-            if (tid < 2) pr[tid] = tid == 0 ? M : L;
-            pr[2 + tid] = O;
-        }
-    }
+    combine_groups<HD, GROUPS>(g, 8 * l8, m, l, acc, a.o, a.part, nh, nh * a.part_stride + split, nsplit);
 }
 
 __global__ __launch_bounds__(NT) void persimmon_cached_kernel(PcArgs a) {
     persimmon_cached_body(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
 }
 
-// nsplit > 1: one workgroup of 64 lanes per (head, row) combines the ranges in range order; p = the (row, head)'s first record
-__device__ __forceinline__ void persimmon_cached_combine_body(const float* __restrict__ p, bf16_t* __restrict__ o, int64_t nh, int nsplit) {
-    const int d = threadIdx.x;
-    float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, p[s * PART]);
-    float L = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-        for (int s = 0; s < nsplit; ++s) {
-            const float ms = p[s * PART];
-            const float f = ms == -INFINITY ? 0.f : __expf(ms - M);
-            L = fmaf(p[s * PART + 1], f, L);
-            O = fmaf(p[s * PART + 2 + d], f, O);
-        }
-    }
-    o[nh * HD + d] = f2bf(L > 0.f ? O / L : 0.f);
-}
-
 __global__ __launch_bounds__(HD) void persimmon_cached_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
     const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    persimmon_cached_combine_body(part + nh * nsplit * PART, o, nh, nsplit);
+    combine_ranges<HD>(part, o, nh, nsplit, nsplit);
 }
 
-// ---- the position in device memory: a launch that does not depend on it ---------------------------------------------------------------
-// The grid is (max_ranges, H, N) for the cache's capacity.  Every workgroup reads the position, derives the ranges of that position by the
-// rule the host uses for the scalar entry point, and leaves at once when its range is not live (or the position is outside [1, S_max): a
-// corrupt counter does nothing, it never indexes the cache).  The whole workgroup takes the same branch, before any barrier.
+// ---- the position in device memory (decode_split.h): grid (max_ranges, H, N) for the capacity --------------------------------------------
 __global__ __launch_bounds__(NT) void persimmon_cached_dyn_kernel(PcArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus, int64_t table_rs) {
-    const int pos = *pos_dev;
-    if (pos < 1 || pos >= S_max) return;
-    const PcSplit sp = pc_split((int64_t)pos + 1, (int64_t)a.N * a.H, cus);
+    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)a.N * a.H, cus);
     if ((int)blockIdx.x >= sp.nsplit) return;
     persimmon_cached_body(a, blockIdx.x, pos, sp.nsplit, sp.kps, a.cs + (int64_t)pos * table_rs, a.sn + (int64_t)pos * table_rs);   // row `pos` of the tables
 }
@@ -241,41 +127,43 @@ __global__ __launch_bounds__(NT) void persimmon_cached_dyn_kernel(PcArgs a, cons
 __global__ __launch_bounds__(HD) void persimmon_cached_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
                                                                           const int32_t* __restrict__ pos_dev, int N, int H, int S_max, int cus,
                                                                           int max_ranges) {
-    const int pos = *pos_dev;
-    if (pos < 1 || pos >= S_max) return;
-    const int nsplit = min(pc_split((int64_t)pos + 1, (int64_t)N * H, cus).nsplit, max_ranges);
+    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)N * H, cus);
+    const int nsplit = min(sp.nsplit, max_ranges);
     if (nsplit == 1) return;                              // the one live workgroup wrote o itself
     const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    persimmon_cached_combine_body(part + nh * max_ranges * PART, o, nh, nsplit);
-}
-
-int cu_count() {
-    static int counts[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (counts[dev] == 0) {
-        int n = 0;
-        counts[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return counts[dev];
+    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
 }
 
 bool mult8(int64_t a, int64_t b) { return a % 8 == 0 && b % 8 == 0; }
 
-void fill_args(PcArgs& a, const void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k, const float* cs,
-               const float* sn, void* k_cache, int64_t k_rs, int64_t k_hs, void* v_cache, int64_t v_rs, int64_t v_hs, const int32_t* src,
-               int64_t src_rs, const uint8_t* key_valid, int64_t kv_rs, void* o, void* workspace, int64_t N, int64_t H, int64_t rot, float eps,
-               float scale) {
-    a.qkv = (const bf16_t*)qkv;
-    a.gq = gamma_q; a.bq = beta_q; a.gk = gamma_k; a.bk = beta_k; a.cs = cs; a.sn = sn;
-    a.kc = (bf16_t*)k_cache; a.kc_rs = k_rs; a.kc_hs = k_hs;
-    a.vc = (bf16_t*)v_cache; a.vc_rs = v_rs; a.vc_hs = v_hs;
-    a.src = src; a.src_rs = src_rs; a.kvalid = key_valid; a.kv_rs = kv_rs;
-    a.o = (bf16_t*)o; a.part = (float*)workspace;
-    a.N = (int)N; a.H = (int)H; a.rot = (int)rot; a.eps = eps; a.scale = scale;
-}
-
 }  // namespace
+
+// the argument checks both entry points share (NAME: the entry point's name in messages).  Three macros where decode_cache_i8.hip has one:
+// here the scalar entry point checks `pos` between the shape and the alignment checks and the dyn one checks `pos_dev` between the alignment
+// and the stride checks, and the order of the checks is part of the ABI (the first failing check names the error).
+#define PC_REQUIRE_SHAPE(NAME)                                                                                                \
+    OTTER_REQUIRE(head_dim == HD, NAME ": head_dim %ld (64 only)", (long)head_dim);                                          \
+    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, NAME ": bad shape N=%ld H=%ld", (long)N, (long)H);              \
+    OTTER_REQUIRE(rot > 0 && rot <= HD && rot % 16 == 0, NAME ": rot=%ld must be a multiple of 16 in (0, 64]", (long)rot);    \
+    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, NAME ": S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT)
+
+#define PC_REQUIRE_ALIGNED(NAME) \
+    OTTER_REQUIRE((((uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0, NAME ": qkv, k_cache, v_cache need 16-byte alignment")
+
+#define PC_REQUIRE_STRIDES(NAME)                                                                                                               \
+    OTTER_REQUIRE(mult8(k_cache_row_stride, k_cache_head_stride) && mult8(v_cache_row_stride, v_cache_head_stride),                            \
+                  NAME ": cache strides must be multiples of 8 elements");                                                                    \
+    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0, \
+                  NAME ": a cache head stride below S_max * 64 would make the slots of two heads overlap")
+
+#define PC_FILL_ARGS(a)                                                                                  \
+    a.qkv = (const bf16_t*)qkv;                                                                          \
+    a.gq = gamma_q; a.bq = beta_q; a.gk = gamma_k; a.bk = beta_k;                                        \
+    a.kc = (bf16_t*)k_cache; a.kc_rs = k_cache_row_stride; a.kc_hs = k_cache_head_stride;                \
+    a.vc = (bf16_t*)v_cache; a.vc_rs = v_cache_row_stride; a.vc_hs = v_cache_head_stride;                \
+    a.src = src; a.src_rs = src_row_stride; a.kvalid = key_valid; a.kv_rs = key_valid_row_stride;        \
+    a.o = (bf16_t*)o; a.part = (float*)workspace;                                                        \
+    a.N = (int)N; a.H = (int)H; a.rot = (int)rot; a.eps = eps; a.scale = scale
 
 extern "C" {
 
@@ -287,30 +175,23 @@ int otter_persimmon_decode_attn_cached(const void* qkv, const float* gamma_q, co
                                        int64_t rot, float eps, float scale, void* stream) {
     OTTER_REQUIRE(qkv && gamma_q && beta_q && gamma_k && beta_k && cos_row && sin_row && k_cache && v_cache && o && workspace,
                   "persimmon_decode_attn_cached: null pointer");
-    OTTER_REQUIRE(head_dim == HD, "persimmon_decode_attn_cached: head_dim %ld (64 only)", (long)head_dim);
-    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, "persimmon_decode_attn_cached: bad shape N=%ld H=%ld", (long)N, (long)H);
-    OTTER_REQUIRE(rot > 0 && rot <= HD && rot % 16 == 0, "persimmon_decode_attn_cached: rot=%ld must be a multiple of 16 in (0, 64]", (long)rot);
-    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, "persimmon_decode_attn_cached: S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT);
+    PC_REQUIRE_SHAPE("persimmon_decode_attn_cached");
     OTTER_REQUIRE(pos >= 1, "persimmon_decode_attn_cached: pos=%ld: a cached step continues a cache (pos >= 1)", (long)pos);
     OTTER_REQUIRE(pos < S_max, "persimmon_decode_attn_cached: pos=%ld is beyond the cache capacity S_max=%ld", (long)pos, (long)S_max);
-    OTTER_REQUIRE((((uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,
-                  "persimmon_decode_attn_cached: qkv, k_cache, v_cache need 16-byte alignment");
-    OTTER_REQUIRE(mult8(k_cache_row_stride, k_cache_head_stride) && mult8(v_cache_row_stride, v_cache_head_stride),
-                  "persimmon_decode_attn_cached: cache strides must be multiples of 8 elements");
-    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0,
-                  "persimmon_decode_attn_cached: a cache head stride below S_max * 64 would make the slots of two heads overlap");
+    PC_REQUIRE_ALIGNED("persimmon_decode_attn_cached");
+    PC_REQUIRE_STRIDES("persimmon_decode_attn_cached");
     OTTER_REQUIRE((!src || src_row_stride >= pos) && (!key_valid || key_valid_row_stride >= pos + 1),
                   "persimmon_decode_attn_cached: src needs a row stride >= pos, key_valid one >= pos + 1");
     const int64_t Sk = pos + 1;
     const int64_t need = OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES(N, H, Sk);
     OTTER_REQUIRE(workspace_bytes >= need, "persimmon_decode_attn_cached: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
 
-    const PcSplit sp = pc_split(Sk, N * H, cu_count());
+    const Split sp = split_rule<KEYS_PER_ITER>(Sk, N * H, cu_count());
     const int64_t nsplit = sp.nsplit;
 
     PcArgs a;
-    fill_args(a, qkv, gamma_q, beta_q, gamma_k, beta_k, cos_row, sin_row, k_cache, k_cache_row_stride, k_cache_head_stride, v_cache,
-              v_cache_row_stride, v_cache_head_stride, src, src_row_stride, key_valid, key_valid_row_stride, o, workspace, N, H, rot, eps, scale);
+    PC_FILL_ARGS(a);
+    a.cs = cos_row; a.sn = sin_row;
     a.pos = (int)pos; a.nsplit = (int)nsplit; a.kps = sp.kps; a.part_stride = (int)nsplit;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(persimmon_cached_kernel, dim3((unsigned)nsplit, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a);
@@ -332,19 +213,10 @@ int otter_persimmon_decode_attn_cached_dyn(const void* qkv, const float* gamma_q
                                            void* stream) {
     OTTER_REQUIRE(qkv && gamma_q && beta_q && gamma_k && beta_k && cos_table && sin_table && k_cache && v_cache && o && workspace && pos_dev,
                   "persimmon_decode_attn_cached_dyn: null pointer");
-    OTTER_REQUIRE(head_dim == HD, "persimmon_decode_attn_cached_dyn: head_dim %ld (64 only)", (long)head_dim);
-    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, "persimmon_decode_attn_cached_dyn: bad shape N=%ld H=%ld", (long)N, (long)H);
-    OTTER_REQUIRE(rot > 0 && rot <= HD && rot % 16 == 0, "persimmon_decode_attn_cached_dyn: rot=%ld must be a multiple of 16 in (0, 64]",
-                  (long)rot);
-    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, "persimmon_decode_attn_cached_dyn: S_max=%ld outside [2, %ld]", (long)S_max,
-                  (long)S_MAX_LIMIT);
-    OTTER_REQUIRE((((uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,
-                  "persimmon_decode_attn_cached_dyn: qkv, k_cache, v_cache need 16-byte alignment");
+    PC_REQUIRE_SHAPE("persimmon_decode_attn_cached_dyn");
+    PC_REQUIRE_ALIGNED("persimmon_decode_attn_cached_dyn");
     OTTER_REQUIRE(((uintptr_t)pos_dev & 3) == 0, "persimmon_decode_attn_cached_dyn: pos_dev needs 4-byte alignment");
-    OTTER_REQUIRE(mult8(k_cache_row_stride, k_cache_head_stride) && mult8(v_cache_row_stride, v_cache_head_stride),
-                  "persimmon_decode_attn_cached_dyn: cache strides must be multiples of 8 elements");
-    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0,
-                  "persimmon_decode_attn_cached_dyn: a cache head stride below S_max * 64 would make the slots of two heads overlap");
+    PC_REQUIRE_STRIDES("persimmon_decode_attn_cached_dyn");
     // any position below S_max may be read from pos_dev: the tables, the beam table and the mask must hold the capacity
     OTTER_REQUIRE(table_row_stride >= rot && (!src || src_row_stride >= S_max - 1) && (!key_valid || key_valid_row_stride >= S_max),
                   "persimmon_decode_attn_cached_dyn: cos / sin tables need a row stride >= rot, src one >= S_max - 1, key_valid one >= S_max");
@@ -352,13 +224,12 @@ int otter_persimmon_decode_attn_cached_dyn(const void* qkv, const float* gamma_q
     OTTER_REQUIRE(workspace_bytes >= need, "persimmon_decode_attn_cached_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes,
                   (long)need);
 
-    // the CU count is looked up once per device (a step that is to be captured has run eagerly before: no device query under capture)
     const int cus = cu_count();
-    const int64_t max_ranges = pc_max_ranges(S_max, N * H, cus);
+    const int64_t max_ranges = split_max_ranges(S_max, N * H, cus);
 
     PcArgs a;
-    fill_args(a, qkv, gamma_q, beta_q, gamma_k, beta_k, cos_table, sin_table, k_cache, k_cache_row_stride, k_cache_head_stride, v_cache,
-              v_cache_row_stride, v_cache_head_stride, src, src_row_stride, key_valid, key_valid_row_stride, o, workspace, N, H, rot, eps, scale);
+    PC_FILL_ARGS(a);
+    a.cs = cos_table; a.sn = sin_table;
     a.pos = 0; a.nsplit = 0; a.kps = 0; a.part_stride = (int)max_ranges;   // (pos, nsplit, kps: read and derived on the device)
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(persimmon_cached_dyn_kernel, dim3((unsigned)max_ranges, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a, pos_dev, (int)S_max,
@@ -373,3 +244,8 @@ int otter_persimmon_decode_attn_cached_dyn(const void* qkv, const float* gamma_q
 }
 
 }  // extern "C"
+
+#undef PC_REQUIRE_SHAPE
+#undef PC_REQUIRE_ALIGNED
+#undef PC_REQUIRE_STRIDES
+#undef PC_FILL_ARGS
