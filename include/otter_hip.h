@@ -551,6 +551,30 @@ int otter_gemm_w8_rows(const void* x, int64_t ldx, const void* qweight, int64_t 
 int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_logits_process -- the tensor-valued logits processors of generate() (otter_amd/generation.py: _Processors) in one launch per
+ * step, in place on the score matrix, from the token history on the device.  One workgroup per row; no allocation, no synchronise.
+ *   scores   fp32 [N, V] with a row stride (elements, >= V), 4-byte aligned.  1 <= V <= 262144 (a V-bit bitmap in LDS).
+ *   ids      int64 [N, L] with a row stride (elements, >= L), 8-byte aligned.  1 <= L <= 2^30.
+ * Applied in this order:
+ *   1. repetition_penalty p (finite, > 0; 1 = off): for every DISTINCT token t of ids[r, 0:L], s = scores[r, t] becomes s * p if s < 0,
+ *      else s * (1.0f / p) -- the reciprocal form is what torch's device kernel computes for `tensor / Python scalar`.  A token that
+ *      occurs k times is penalised once.
+ *   2. no_repeat_ngram n (>= 0; 0 = off), only when L + 1 >= n.  n == 1: every token of the row is banned.  n > 1: ids[r, i + n - 1] is
+ *      banned for every 0 <= i <= L - n with ids[r, i : i + n - 1] == ids[r, L - n + 1 : L].
+ *   3. ban: int32 [n_ban], banned in every row.
+ *   4. words: word w is word_tokens[word_offsets[w] : word_offsets[w + 1]] (int32; word_offsets int32 [n_words + 1], non-decreasing,
+ *      inside word_tokens).  A word of m >= 2 tokens bans its last token in row r if m - 1 <= L and the row ends in its first m - 1
+ *      tokens; shorter words are ignored.
+ *   5. eos: int32 [n_eos], banned in every row when suppress_eos != 0 (the host decides it from L, min_length and min_new_tokens).
+ * A ban stores -inf and wins over the penalty.  A token outside [0, V), in ids or in a list, penalises nothing, bans nothing and is
+ * never used as an index; as a value it still takes part in the n-gram and word comparisons.  List pointers may be NULL when their
+ * count is 0; they are 4-byte aligned.
+ * ------------------------------------------------------------------------------------------------------- */
+int otter_logits_process(float* scores, int64_t scores_stride, const int64_t* ids, int64_t ids_stride, int64_t N, int64_t V, int64_t L,
+                         float repetition_penalty, int no_repeat_ngram, const int32_t* ban, int64_t n_ban, const int32_t* eos, int64_t n_eos,
+                         int suppress_eos, const int32_t* word_tokens, const int32_t* word_offsets, int64_t n_words, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * OtterHD / Fuyu-8B path (config C5): row-wise kernels of the Persimmon decoder and the patch scatter.
  *   otter_qk_norm_rope_fwd  /root/reference/src/otter_ai/models/fuyu/modeling_persimmon.py:262-304: the per-head interleaved
  *       projection output qkv [tokens, H, 3, 64] (bf16) is read in place; q and k get LayerNorm over the 64-wide head

@@ -12,13 +12,19 @@ restated: constrained beam search (`constraints` / `force_words_ids`), contrasti
 (generation/utils.py beam_search + generation/beam_search.py BeamSearchScorer + generation/logits_process.py), restated on
 plain tensors around a `step` callback so that it serves both decoder hosts and both decode modes (KV cache or full
 re-forward).  Pinned by tests/test_generation.py against `transformers`' own generate() on a shared tiny LLaMA.
+
+On device tensors the tensor-valued logits processors are one HIP launch per step (`ops.logits_process`, csrc/logits.hip; OTTER_HIP_LOGITS=0
+switches back); the host loop below is the only path for CPU tensors and the reference that kernel is tested against, bit for bit.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
+
+from . import ops
 
 NEG_INF = float("-inf")
 
@@ -78,6 +84,19 @@ def _top_k_top_p(scores: torch.Tensor, top_k: int, top_p: float, min_keep: int =
     return scores
 
 
+def pack_bad_words(bad_words: Sequence[Sequence[int]]) -> Tuple[List[int], List[int], List[int]]:
+    """The lists ops.logits_process reads, from bad words as `_Processors` filtered them: (the one-token words, the tokens of the words of two
+    or more tokens laid end to end, their offsets [words + 1]); word i is tokens[offsets[i] : offsets[i + 1]], in the order given."""
+    single = [int(w[0]) for w in bad_words if len(w) == 1]
+    tokens: List[int] = []
+    offsets = [0]
+    for w in bad_words:
+        if len(w) > 1:
+            tokens += [int(t) for t in w]
+            offsets.append(len(tokens))
+    return single, tokens, offsets
+
+
 class _Processors:
     def __init__(self, prompt_len: int, eos: List[int], repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_new_tokens, min_length,
                  prefix_allowed_tokens_fn=None, beams_per_sentence: int = 1):
@@ -88,16 +107,49 @@ class _Processors:
         self.bad = [list(w) for w in (bad_words_ids or []) if list(w) != eos[:1] and not (len(w) == 1 and w[0] in eos)]
         self.min_new = int(min_new_tokens or 0)
         self.min_len = int(min_length or 0)
+        self._lists = None             # the device lists of the HIP path, built on its first call: (device, V, ban, eos, tokens, offsets) or False
+
+    def _device_lists(self, dev, V: int):
+        """ban / eos / word tokens / word offsets as int32 tensors on `dev` (None for an empty list), built once.  False when the HIP kernel
+        cannot state what the host loop does with them: it skips a listed token outside [0, V) where indexing wraps a negative one and raises
+        on the rest, and a penalty it refuses (<= 0 or not finite as an fp32 number) is the host loop's to apply."""
+        if self._lists is None or (self._lists is not False and self._lists[:2] != (dev, V)):
+            single, tokens, offsets = pack_bad_words(self.bad)
+            eos = list(self.eos) if (self.min_len > 0 or self.min_new > 0) else []      # (never suppressed otherwise)
+            last = [tokens[o - 1] for o in offsets[1:]]
+            if (any(not 0 <= t < V for t in single + eos + last) or any(not -2 ** 31 <= t < 2 ** 31 for t in tokens)
+                    or (self.rp is not None and not (1e-30 < self.rp < 1e30))):
+                self._lists = False
+            else:
+                i32 = lambda l: torch.tensor(l, dtype=torch.int32, device=dev) if l else None
+                self._lists = (dev, V, i32(single), i32(eos), i32(tokens), i32(offsets) if tokens else None)
+        return self._lists
+
+    def _hip(self, ids: torch.Tensor, scores: torch.Tensor) -> bool:
+        """The tensor-valued processors in one launch of ops.logits_process, in place on `scores`; False: not taken, the host loop runs."""
+        if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1 and ids.device == scores.device
+                and ids.dtype == torch.int64 and ids.stride(1) == 1 and 1 <= scores.shape[1] <= ops.LOGITS_PROCESS_MAX_VOCAB
+                and ids.shape[1] >= 1 and scores.shape[0] >= 1 and os.environ.get("OTTER_HIP_LOGITS", "1") != "0"):
+            return False
+        lists = self._device_lists(scores.device, scores.shape[1])
+        if lists is False:
+            return False
+        suppress = bool(self.eos) and (ids.shape[1] < self.min_len or ids.shape[1] - self.prompt_len < self.min_new)
+        if self.rp is not None or self.ngram > 0 or self.bad or suppress:
+            ops.logits_process(scores, ids, self.rp if self.rp is not None else 1.0, max(self.ngram, 0), lists[2], lists[3], suppress, lists[4],
+                               lists[5])
+        return True
 
     def __call__(self, ids: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
-        if self.rp is not None:
-            scores = _repetition_penalty(ids, scores, self.rp)
-        if self.ngram > 0:
-            scores = _no_repeat_ngram(ids, scores, self.ngram)
-        if self.bad:
-            scores = _no_bad_words(ids, scores, self.bad)
-        if self.eos and (ids.shape[1] < self.min_len or ids.shape[1] - self.prompt_len < self.min_new):
-            scores[:, self.eos] = NEG_INF
+        if not self._hip(ids, scores):     # CPU tensors, OTTER_HIP_LOGITS=0, a vocabulary past the kernel's cap: the host loop, the reference
+            if self.rp is not None:
+                scores = _repetition_penalty(ids, scores, self.rp)
+            if self.ngram > 0:
+                scores = _no_repeat_ngram(ids, scores, self.ngram)
+            if self.bad:
+                scores = _no_bad_words(ids, scores, self.bad)
+            if self.eos and (ids.shape[1] < self.min_len or ids.shape[1] - self.prompt_len < self.min_new):
+                scores[:, self.eos] = NEG_INF
         if self.prefix_fn is not None:
             # PrefixConstrainedLogitsProcessor: fn(sentence index, tokens so far) -> the ids allowed next; rows are [sentence][beam]
             keep = torch.full_like(scores, NEG_INF)

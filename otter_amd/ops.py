@@ -1000,6 +1000,48 @@ def dequant_w8(qweight, scale, out=None):
     return out
 
 
+LOGITS_PROCESS_MAX_VOCAB = 262144     # include/otter_hip.h: the V-bit ownership bitmap of otter_logits_process
+
+
+def _i32_list(name, t, device):
+    """(pointer, length) of an optional contiguous int32 1-d list on `device`."""
+    if t is None or t.numel() == 0:
+        return None, 0
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
+        raise K.OtterHipError(f"logits_process: {name} must be a contiguous int32 1-d tensor on the scores' device")
+    return t.data_ptr(), t.numel()
+
+
+def logits_process(scores, ids, repetition_penalty=1.0, no_repeat_ngram=0, ban=None, eos=None, suppress_eos=False, word_tokens=None,
+                   word_offsets=None):
+    """The logits processors of generate() in one launch, IN PLACE on scores fp32 [N, V] (unit column stride, V <= LOGITS_PROCESS_MAX_VOCAB)
+    from the token history ids int64 [N, L] on the same device (otter_logits_process, csrc/logits.hip): repetition penalty (1 = off), no-repeat
+    n-gram (0 = off), the always-banned int32 list `ban`, the multi-token bad words (`word_tokens` int32 flat, `word_offsets` int32
+    [words + 1]) and the int32 `eos` list when `suppress_eos`.  Nothing here synchronises.  Returns scores."""
+    K.require_cuda(scores, ids, ban, eos, word_tokens, word_offsets)
+    if scores.dim() != 2 or ids.dim() != 2 or scores.shape[0] != ids.shape[0] or scores.device != ids.device:
+        raise K.OtterHipError("logits_process: scores [N, V] and ids [N, L] of equal N on one device")
+    if scores.dtype != torch.float32 or ids.dtype != torch.int64 or scores.stride(1) != 1 or ids.stride(1) != 1:
+        raise K.OtterHipError("logits_process: scores fp32 and ids int64, both with a unit column stride")
+    N, V = scores.shape
+    L = ids.shape[1]
+    if N < 1 or L < 1 or not 1 <= V <= LOGITS_PROCESS_MAX_VOCAB:
+        raise K.OtterHipError(f"logits_process: N={N}, L={L} must be >= 1 and V={V} within 1..{LOGITS_PROCESS_MAX_VOCAB}")
+    dev = scores.device
+    ban_p, n_ban = _i32_list("ban", ban, dev)
+    eos_p, n_eos = _i32_list("eos", eos, dev)
+    tok_p, _ = _i32_list("word_tokens", word_tokens, dev)
+    off_p, n_off = _i32_list("word_offsets", word_offsets, dev)
+    if (tok_p is None) != (off_p is None) or n_off == 1:
+        raise K.OtterHipError("logits_process: word_tokens and word_offsets (int32 [words + 1]) are given together or not at all")
+    s_rs = scores.stride(0) if N > 1 else max(scores.stride(0), V)      # (the row stride of a one-row view is arbitrary)
+    i_rs = ids.stride(0) if N > 1 else max(ids.stride(0), L)
+    K.check(K.lib().otter_logits_process(scores.data_ptr(), s_rs, ids.data_ptr(), i_rs, N, V, L, float(repetition_penalty), int(no_repeat_ngram),
+                                         ban_p, n_ban, eos_p, n_eos, int(bool(suppress_eos)), tok_p, off_p, max(n_off - 1, 0), K.stream()),
+            "logits_process")
+    return scores
+
+
 def qk_norm_rope_fwd(qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, width=128, copy_v=True):
     """qkv [B,S,H*3*64] bf16 (per head q|k|v) -> q', k', v as [B,S,H,width] bf16, stats [B*S,H,2,2].  width 128: upper 64 columns zero
     (the 128-wide flash kernels); width 64: compact heads (the head-pair kernels), and with copy_v=False v is returned as the strided
