@@ -575,6 +575,43 @@ int otter_logits_process(float* scores, int64_t scores_stride, const int64_t* id
                          int suppress_eos, const int32_t* word_tokens, const int32_t* word_offsets, int64_t n_words, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_beam_step -- one beam-search step of generate() (otter_amd/generation.py: generate_tokens, num_beams > 1 without sampling or
+ * groups) in two launches: the n_cand best continuations of every sentence, BeamSearchScorer.process with its hypothesis lists, and the
+ * reordered token history.  No allocation, no synchronise, no device query; all state is the caller's, at fixed addresses.
+ *   logp         fp32 [B * nb, V], row stride (elements, >= V): the processed log-probabilities.  Read only.
+ *   beam_scores  fp32 [B * nb], in and out.
+ *   ids          int64 [B * nb, L], row stride (>= L): the history.  ids_next int64 [B * nb, L + 1], row stride (>= L + 1), not overlapping
+ *                ids: row r becomes ids[beam_idx[r], 0:L] followed by the new token.  beam_idx int64 [B * nb], out.
+ *   eos          int32 [n_eos], NULL when n_eos == 0.  pad_token_id fills the beams of a finished sentence.
+ *   n_cand       the host's max(2, 1 + n_eos) * nb; nb <= n_cand <= min(nb * V, OTTER_BEAM_STEP_MAX_CANDIDATES).
+ *   L0, max_len  the prompt length and the length generation stops at; 1 <= L0 <= L < max_len.
+ *   early_stopping  0 = False, 1 = True, 2 = "never"; length_penalty_positive: whether length_penalty > 0 (read by "never" only).
+ *   len_pow      fp64 [max_len - L0 + 1]: len_pow[g] = float(g) ** length_penalty as the host computed it (entry 0 is never read).
+ * Selection: for sentence b the n_cand largest of logp[b * nb + j, t] + beam_scores[b * nb + j] (one fp32 add), in descending order.
+ * TIE RULE: the larger sum first; among equal sums the smaller flat index j * V + t first.  -inf is an ordinary value, -0 equals +0;
+ * NaN sums are outside the contract.
+ * Scorer, candidate by candidate in that order until nb beams are filled: an eos candidate at rank >= nb is skipped; at rank < nb it
+ * adds ids[b * nb + j, 0:L] as a hypothesis of generated length L + 1 - L0; any other candidate becomes the next beam (sum, token,
+ * source row).  Beams left unfilled get (0, pad_token_id, row 0); a finished sentence gets (0, pad_token_id, row b * nb) in every beam.
+ * Then done[b] |= is_done(best sum of the step).  Hypothesis arithmetic is fp64: score = (double)sum / len_pow[generated length].
+ * State (zero before the first step unless noted), nb entries per sentence:
+ *   hyp_score fp64 [B, nb], hyp_len int32 [B, nb], hyp_slot int32 [B, nb]: the list of sentence b IN INSERTION ORDER, hyp_count[b]
+ *       entries long; entry i's tokens are hyp_tokens[b, hyp_slot[b, i], 0:hyp_len[b, i]] (hyp_tokens int64 [B, nb, max_len]).  An entry
+ *       is added when the list is short or its score exceeds hyp_worst[b]; a full list then drops its lowest (score, list index) and
+ *       hyp_worst[b] becomes the second lowest score, otherwise hyp_worst[b] = min(score, hyp_worst[b]).  hyp_worst fp64 [B] starts at 1e9.
+ *   done int32 [B]; all_done int32 [2]: all_done[0] = every sentence is done, all_done[1] = how many are.
+ *   workspace    at least otter_beam_step_workspace_bytes(B, nb, V, n_cand) bytes (-1: arguments out of range), 8-byte aligned.
+ * Limits: nb * V <= 2^31 - 1, B * nb <= 65535.
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_BEAM_STEP_MAX_CANDIDATES 64
+int64_t otter_beam_step_workspace_bytes(int64_t B, int64_t nb, int64_t V, int64_t n_cand);
+int otter_beam_step(const float* logp, int64_t logp_stride, float* beam_scores, const int64_t* ids, int64_t ids_stride, int64_t* ids_next,
+                    int64_t ids_next_stride, int64_t* beam_idx, const int32_t* eos, int64_t n_eos, int64_t pad_token_id, int64_t B, int64_t nb,
+                    int64_t V, int64_t n_cand, int64_t L, int64_t L0, int64_t max_len, int early_stopping, int length_penalty_positive,
+                    const double* len_pow, int32_t* done, double* hyp_score, int64_t* hyp_tokens, int32_t* hyp_len, int32_t* hyp_slot,
+                    int32_t* hyp_count, double* hyp_worst, int32_t* all_done, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * OtterHD / Fuyu-8B path (config C5): row-wise kernels of the Persimmon decoder and the patch scatter.
  *   otter_qk_norm_rope_fwd  /root/reference/src/otter_ai/models/fuyu/modeling_persimmon.py:262-304: the per-head interleaved
  *       projection output qkv [tokens, H, 3, 64] (bf16) is read in place; q and k get LayerNorm over the 64-wide head

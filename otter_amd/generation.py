@@ -14,7 +14,9 @@ plain tensors around a `step` callback so that it serves both decoder hosts and 
 re-forward).  Pinned by tests/test_generation.py against `transformers`' own generate() on a shared tiny LLaMA.
 
 On device tensors the tensor-valued logits processors are one HIP launch per step (`ops.logits_process`, csrc/logits.hip; OTTER_HIP_LOGITS=0
-switches back); the host loop below is the only path for CPU tensors and the reference that kernel is tested against, bit for bit.
+switches back); the host loop below is the only path for CPU tensors and the reference that kernel is tested against, bit for bit.  Plain beam
+search on device tensors likewise runs candidate selection, the scorer and the reorder in `ops.beam_step` (csrc/beam.hip, `_DeviceBeam`;
+OTTER_HIP_BEAM=0 switches back to the host block, which stays the path of CPU tensors, beam-sample and group beam search).
 """
 from __future__ import annotations
 
@@ -198,6 +200,107 @@ class _BeamHyps:
         return self.worst >= best_sum_logprobs / (cur_len - prompt_len) ** self.lp
 
 
+def beam_len_pow(n: int, length_penalty: float) -> List[float]:
+    """len_pow[g] = float(g) ** length_penalty for 0 <= g < n -- `generated_len ** self.lp` of _BeamHyps.add as Python evaluates it, so that the
+    device divides by the host's own bits.  Entry 0 is never read (a hypothesis has at least one generated token); a negative penalty gives it inf."""
+    lp = float(length_penalty)
+    out = []
+    for g in range(n):
+        try:
+            out.append(float(g) ** lp)
+        except ZeroDivisionError:
+            out.append(math.inf)
+    return out
+
+
+def rebuild_beam_hyps(nb: int, length_penalty: float, early_stopping, count: int, scores: Sequence[float], lens: Sequence[int],
+                      slots: Sequence[int], worst: float, tokens: torch.Tensor) -> _BeamHyps:
+    """The _BeamHyps of one sentence from the state ops.beam_step keeps: `beams` in list order -- entry i is (scores[i], tokens[slots[i],
+    :lens[i]]), tokens [nb, max_len] on any device -- and `worst`."""
+    h = _BeamHyps(nb, length_penalty, early_stopping)
+    h.beams = [(float(scores[i]), tokens[int(slots[i]), :int(lens[i])]) for i in range(int(count))]
+    h.worst = float(worst)
+    return h
+
+
+class _DeviceBeam:
+    """The state of one beam search on the device, allocated once per generate_tokens call at fixed addresses: the scalars of the scorer in ONE
+    byte blob (so that one copy brings them to the host after the loop), the hypotheses' token rows, the ping-pong token history
+    [2, N, max_len], beam_idx, the length-penalty table and the kernel's workspace.  `step` is one ops.beam_step call and nothing else."""
+
+    FIELDS = (("hyp_score", torch.float64, "N"), ("hyp_worst", torch.float64, "B"), ("beam_scores", torch.float32, "N"),
+              ("hyp_len", torch.int32, "N"), ("hyp_slot", torch.int32, "N"), ("hyp_count", torch.int32, "B"), ("done", torch.int32, "B"),
+              ("all_done", torch.int32, 2))
+
+    @classmethod
+    def carve(cls, blob: Optional[torch.Tensor], B: int, nb: int):
+        """(views of `blob` by field name, the blob's size in bytes); every field starts on an 8-byte boundary."""
+        views, off = {}, 0
+        for name, dtype, n in cls.FIELDS:
+            n = {"N": B * nb, "B": B}.get(n, n)
+            size = n * torch.empty(0, dtype=dtype).element_size()
+            if blob is not None:
+                views[name] = blob[off:off + size].view(dtype)
+            off += (size + 7) // 8 * 8
+        return views, off
+
+    @staticmethod
+    def usable(logp: torch.Tensor, ids: torch.Tensor, nb: int, n_cand: int) -> bool:
+        return (logp.is_cuda and logp.dtype == torch.float32 and logp.dim() == 2 and logp.stride(1) == 1 and ids.device == logp.device
+                and ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 and ids.shape[1] >= 1 and ids.shape[0] == logp.shape[0]
+                and n_cand <= ops.BEAM_STEP_MAX_CANDIDATES and n_cand <= nb * logp.shape[1] and nb * logp.shape[1] < 2 ** 31
+                and logp.shape[0] <= 65535 and os.environ.get("OTTER_HIP_BEAM", "1") != "0")
+
+    def __init__(self, B: int, nb: int, V: int, L0: int, max_len: int, eos: List[int], pad_token_id: int, length_penalty: float, early_stopping,
+                 beam_scores: torch.Tensor):
+        dev = beam_scores.device
+        self.B, self.nb, self.L0, self.max_len, self.eos, self.pad = B, nb, L0, max_len, eos, int(pad_token_id)
+        self.lp, self.early = float(length_penalty), early_stopping
+        self.n_cand = max(2, 1 + len(eos)) * nb
+        N = B * nb
+        _, size = self.carve(None, B, nb)
+        host = torch.zeros(size, dtype=torch.uint8)
+        v, _ = self.carve(host, B, nb)
+        v["hyp_worst"].fill_(1e9)
+        self.blob = host.to(dev)
+        self.v, _ = self.carve(self.blob, B, nb)
+        self.v["beam_scores"].copy_(beam_scores)
+        self.len_pow = torch.tensor(beam_len_pow(max_len - L0 + 1, self.lp), dtype=torch.float64).to(dev)
+        self.eos_t = torch.tensor(eos, dtype=torch.int32).to(dev) if eos else None
+        self.hyp_tokens = torch.zeros(B, nb, max_len, dtype=torch.int64, device=dev)
+        self.ids_buf = torch.zeros(2, N, max_len, dtype=torch.int64, device=dev)
+        self.beam_idx = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.workspace = torch.empty(ops.beam_step_workspace_bytes(B, nb, V, self.n_cand), dtype=torch.uint8, device=dev)
+        self.steps = 0
+
+    def step(self, logp: torch.Tensor, ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(the next ids [N, L + 1], a view of the other half of the ping-pong buffer; beam_idx [N])."""
+        v = self.v
+        nxt = self.ids_buf[self.steps % 2][:, :ids.shape[1] + 1]
+        self.steps += 1
+        if logp.stride(1) != 1:
+            logp = logp.contiguous()
+        ops.beam_step(logp, v["beam_scores"], ids, nxt, self.beam_idx, self.eos_t, self.pad, self.nb, self.n_cand, self.L0, self.max_len,
+                      self.early, self.lp > 0.0, self.len_pow, v["done"], v["hyp_score"], self.hyp_tokens, v["hyp_len"], v["hyp_slot"],
+                      v["hyp_count"], v["hyp_worst"], v["all_done"], self.workspace)
+        return nxt, self.beam_idx
+
+    def all_done(self) -> bool:
+        """The 4-byte flag: the one synchronising read of a step (made only when an eos list exists -- nothing finishes early without one)."""
+        return bool(self.v["all_done"][0].item())
+
+    def finish(self) -> Tuple[List[_BeamHyps], List[bool], torch.Tensor]:
+        """ONE copy of the scalar state to the host: (the _BeamHyps of every sentence, their token rows views of the device buffer; done; the beam
+        scores as a CPU tensor)."""
+        h, _ = self.carve(self.blob.cpu(), self.B, self.nb)
+        nb = self.nb
+        sc, ln, sl = h["hyp_score"].tolist(), h["hyp_len"].tolist(), h["hyp_slot"].tolist()
+        cnt, worst = h["hyp_count"].tolist(), h["hyp_worst"].tolist()
+        hyps = [rebuild_beam_hyps(nb, self.lp, self.early, cnt[b], sc[b * nb:(b + 1) * nb], ln[b * nb:(b + 1) * nb], sl[b * nb:(b + 1) * nb],
+                                  worst[b], self.hyp_tokens[b]) for b in range(self.B)]
+        return hyps, [bool(d) for d in h["done"].tolist()], h["beam_scores"]
+
+
 # ---- the loop ----------------------------------------------------------------------------------------------------------
 
 # step(ids [N,L], mask [N,L] or None, past, beam_idx [N] or None) -> (last-position logits [N,V], past)
@@ -289,12 +392,24 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
     hyps = [_BeamHyps(nb, float(length_penalty), early_stopping) for _ in range(B)]
     done = [False] * B
     past, beam_idx = None, None
+    dbeam = None                       # the device path's state (_DeviceBeam), decided at the first step from the tensors it would read
     while True:
         logits, past = step(ids, mask, past, beam_idx)
         logp = torch.log_softmax(logits.float(), dim=-1)
         logp = proc(ids, logp)
         V = logp.shape[-1]
         n_cand = max(2, 1 + len(eos)) * nb
+        if dbeam is None and beam_idx is None and not do_sample and _DeviceBeam.usable(logp, ids, nb, n_cand):
+            dbeam = _DeviceBeam(B, nb, V, L0, max_len, eos, pad_token_id, float(length_penalty), early_stopping, beam_scores)
+        if dbeam is not None:
+            # selection, BeamSearchScorer.process and the reorder in one ops.beam_step call (csrc/beam.hip): no .tolist(), no host loop, no
+            # copies back.  ids becomes a [:, :L + 1] view of the ping-pong buffer.
+            ids, beam_idx = dbeam.step(logp, ids)
+            if mask is not None:
+                mask = torch.cat([mask[beam_idx], torch.ones_like(mask[:, :1])], dim=1)
+            if ids.shape[1] >= max_len or (eos and dbeam.all_done()):
+                break
+            continue
         if do_sample:
             # beam-sample (generation/utils.py beam_sample): the warpers act on the processed log-probabilities of each beam (at least as many
             # tokens kept as candidates are drawn per beam pair), candidates are DRAWN from softmax(score + beam score) over all beams of a
@@ -340,6 +455,8 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
             mask = torch.cat([mask[beam_idx], torch.ones_like(mask[:, :1])], dim=1)
         if all(done) or ids.shape[1] >= max_len:
             break
+    if dbeam is not None:
+        hyps, done, beam_scores = dbeam.finish()
     # finalize: open beams of unfinished sentences become hypotheses, best `num_return_sequences` per sentence
     bs = beam_scores.tolist()
     for b in range(B):

@@ -1042,6 +1042,60 @@ def logits_process(scores, ids, repetition_penalty=1.0, no_repeat_ngram=0, ban=N
     return scores
 
 
+BEAM_STEP_MAX_CANDIDATES = 64         # include/otter_hip.h: OTTER_BEAM_STEP_MAX_CANDIDATES, the candidates one wave of otter_beam_step ranks
+
+
+def beam_step_workspace_bytes(B, nb, V, n_cand):
+    """The workspace otter_beam_step needs for B sentences of nb beams over V tokens with n_cand candidates (host arithmetic only)."""
+    n = K.lib().otter_beam_step_workspace_bytes(int(B), int(nb), int(V), int(n_cand))
+    if n < 0:
+        raise K.OtterHipError(f"beam_step: B={B}, nb={nb}, V={V}, n_cand={n_cand} out of range (n_cand <= {BEAM_STEP_MAX_CANDIDATES})")
+    return n
+
+
+def beam_step(logp, beam_scores, ids, ids_next, beam_idx, eos, pad_token_id, nb, n_cand, L0, max_len, early_stopping, length_penalty_positive,
+              len_pow, done, hyp_score, hyp_tokens, hyp_len, hyp_slot, hyp_count, hyp_worst, all_done, workspace):
+    """One beam-search step in two launches (otter_beam_step, csrc/beam.hip; include/otter_hip.h states the semantics and the tie rule): from
+    logp fp32 [B * nb, V] (unit column stride), beam_scores fp32 [B * nb] (in and out) and ids int64 [B * nb, L], the n_cand best continuations
+    per sentence, the scorer with its hypothesis state (hyp_* / done / all_done, the caller's buffers, updated in place) and the outputs
+    ids_next int64 [B * nb, L + 1] (not overlapping ids) and beam_idx int64 [B * nb].  `eos`: int32 list tensor or None; `early_stopping`:
+    True, False or "never".  Nothing here synchronises or allocates."""
+    f32, f64, i32, i64 = torch.float32, torch.float64, torch.int32, torch.int64
+    state = (beam_scores, beam_idx, len_pow, done, hyp_score, hyp_tokens, hyp_len, hyp_slot, hyp_count, hyp_worst, all_done, workspace)
+    K.require_cuda(logp, ids, ids_next, eos, *state)
+    if logp.dim() != 2 or ids.dim() != 2 or ids_next.dim() != 2 or logp.shape[0] != ids.shape[0] or ids_next.shape[0] != ids.shape[0]:
+        raise K.OtterHipError("beam_step: logp [N, V], ids [N, L] and ids_next [N, L + 1] of equal N")
+    if logp.dtype != f32 or ids.dtype != i64 or ids_next.dtype != i64 or logp.stride(1) != 1 or ids.stride(1) != 1 or ids_next.stride(1) != 1:
+        raise K.OtterHipError("beam_step: logp fp32, ids and ids_next int64, all with a unit column stride")
+    N, V = logp.shape
+    L = ids.shape[1]
+    nb, n_cand, L0, max_len = int(nb), int(n_cand), int(L0), int(max_len)
+    if nb < 1 or N < 1 or N % nb != 0 or ids_next.shape[1] != L + 1:
+        raise K.OtterHipError(f"beam_step: N={N} rows must be a positive multiple of nb={nb}, and ids_next [N, L + 1 = {L + 1}]")
+    B = N // nb
+    dev = logp.device
+    want = ((beam_scores, f32, N), (beam_idx, i64, N), (len_pow, f64, max_len - L0 + 1), (done, i32, B), (hyp_score, f64, N),
+            (hyp_tokens, i64, N * max_len), (hyp_len, i32, N), (hyp_slot, i32, N), (hyp_count, i32, B), (hyp_worst, f64, B), (all_done, i32, 2))
+    for t, dtype, numel in want:
+        if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != dev:
+            raise K.OtterHipError("beam_step: state and output buffers must be contiguous, on logp's device, of the dtypes and sizes "
+                                  "include/otter_hip.h states (got %s of %d elements where %s of %d is needed)" % (t.dtype, t.numel(), dtype, numel))
+    if ids.device != dev or ids_next.device != dev or workspace.device != dev or not workspace.is_contiguous():
+        raise K.OtterHipError("beam_step: ids, ids_next and the workspace must be on logp's device (the workspace contiguous)")
+    eos_p, n_eos = _i32_list("eos", eos, dev)
+    early = 1 if early_stopping is True else 0 if early_stopping is False else 2
+    lp_rs = logp.stride(0) if N > 1 else max(logp.stride(0), V)      # (the row stride of a one-row view is arbitrary)
+    i_rs = ids.stride(0) if N > 1 else max(ids.stride(0), L)
+    n_rs = ids_next.stride(0) if N > 1 else max(ids_next.stride(0), L + 1)
+    K.check(K.lib().otter_beam_step(logp.data_ptr(), lp_rs, beam_scores.data_ptr(), ids.data_ptr(), i_rs, ids_next.data_ptr(), n_rs,
+                                    beam_idx.data_ptr(), eos_p, n_eos, int(pad_token_id), B, nb, V, n_cand, L, L0, max_len, early,
+                                    int(bool(length_penalty_positive)), len_pow.data_ptr(), done.data_ptr(), hyp_score.data_ptr(),
+                                    hyp_tokens.data_ptr(), hyp_len.data_ptr(), hyp_slot.data_ptr(), hyp_count.data_ptr(), hyp_worst.data_ptr(),
+                                    all_done.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), K.stream()),
+            "beam_step")
+    return ids_next, beam_idx
+
+
 def qk_norm_rope_fwd(qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, width=128, copy_v=True):
     """qkv [B,S,H*3*64] bf16 (per head q|k|v) -> q', k', v as [B,S,H,width] bf16, stats [B*S,H,2,2].  width 128: upper 64 columns zero
     (the 128-wide flash kernels); width 64: compact heads (the head-pair kernels), and with copy_v=False v is returned as the strided
