@@ -488,10 +488,7 @@ class PersimmonModel(PersimmonPreTrainedModel):
                 x, _, pending = layer(x, cos, sin, hip=True, pending=pending, defer=True, key_valid=key_valid, static=(cache, i, reference))
             else:
                 x, _ = layer(x, cos, sin, key_valid=key_valid, static=(cache, i, reference))
-        if cache.replay:
-            cache.advance()
-        else:
-            cache.length += 1
+        cache.end_step()
         n = self.final_layernorm
         if pending is not None:
             x = OF.add_layer_norm(x, pending, n.weight, n.bias, n.eps, OF.compute_dtype_for(x))[1]

@@ -16,7 +16,8 @@ instead of the cache:
 Replay mode (`enable_replay`, once, after the prefill; `generate(..., graph_decode=True)`): everything a step reads that changes from step to
 step lives at a fixed device address, so that one captured graph of the step can be replayed at every position:
 
-    pos_dev   int32 [1] on the device, equal to `length`; `advance()` increments both (the device add is the last op of the captured step).
+    pos_dev   int32 [1] on the device, equal to `length`; `advance()` increments both (the device add is the last op of the captured step);
+              a host ends every step with `end_step()`: `advance()` here, `length += 1` in the position-scalar mode.
     valid     uint8 [rows, max_len]: the prompt's attention mask in columns [0, S), ones after it (generation only ever appends ones).
     src       created eagerly when beams are in use, so that its address and the NULL / non-NULL choice are fixed before capture.
 
@@ -234,6 +235,13 @@ class StaticKVCache:
         self.pos_dev.add_(1)
         self.length += 1
 
+    def end_step(self) -> None:
+        """The end of a cached step of a host, after the last layer: `advance()` in replay mode, otherwise the host length alone."""
+        if self.replay:
+            self.advance()
+        else:
+            self.length += 1
+
     def note_replay(self) -> None:
         """A captured step was replayed: the graph advanced `pos_dev`, the host length follows."""
         if self.length + 1 > self.max_len:
@@ -320,19 +328,7 @@ class StaticKVCache:
         softmax in fp32 at least, a fully masked row -> 0.  Replay mode: the position is read from `pos_dev` (not from `length`), cos / sin
         are the whole tables, of which row `pos` is taken, and the mask is columns 0..pos of `valid`.  int8 (csrc/decode_cache_i8.hip): the
         rounded k and v are quantised, codes and scales stored, and the gathered codes dequantised -- key `pos` included."""
-        pos, N, H, d = self.length, q.shape[0], q.shape[1], q.shape[2]
-        if self.replay:
-            pos = int(self.pos_dev.item())
-            if key_valid is not None:
-                raise ValueError("StaticKVCache.attend_reference: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
-            key_valid = self.valid
-            if cos is not None:
-                if cos.dim() != 2 or cos.shape[0] < self.max_len:
-                    raise ValueError("StaticKVCache: replay mode takes the whole cos / sin tables [>= max_len, d]")
-                if 0 <= pos < cos.shape[0]:
-                    cos, sin = cos[pos], sin[pos]
-        if pos < 1 or pos >= self.max_len:
-            raise ValueError("StaticKVCache: a cached step needs 1 <= length < max_len (length=%d, max_len=%d)" % (pos, self.max_len))
+        pos, cos, sin, key_valid = self._step_inputs("attend_reference", "d", cos, sin, key_valid)
         ct = torch.float64 if q.dtype == torch.float64 else torch.float32
         qf, kf = q.to(ct), k_new.to(ct)
         if cos is not None:
@@ -344,18 +340,44 @@ class StaticKVCache:
         if self.int8:
             self.k[layer, :, :, pos], self.k_scale[layer, :, :, pos] = quantize_kv_int8(kf.to(self.dtype))
             self.v[layer, :, :, pos], self.v_scale[layer, :, :, pos] = quantize_kv_int8(v_new.to(self.dtype))
-            k = dequantize_kv_int8(self._gathered(self.k[layer], pos + 1), self._gathered(self.k_scale[layer], pos + 1), ct)
-            v = dequantize_kv_int8(self._gathered(self.v[layer], pos + 1), self._gathered(self.v_scale[layer], pos + 1), ct)
         else:
             self.k[layer, :, :, pos] = kf.to(self.dtype)
             self.v[layer, :, :, pos] = v_new.to(self.dtype)
-            k = self._gathered(self.k[layer], pos + 1).to(ct)                  # column pos of the table is the row's own index
-            v = self._gathered(self.v[layer], pos + 1).to(ct)
+        return self._attend_appended(layer, qf, pos, scale, key_valid, slopes, q.dtype)
+
+    def _step_inputs(self, who: str, width: str, cos, sin, key_valid):
+        """(pos, cos, sin, key_valid) as a restatement uses them: `length` and the caller's own, or in replay mode the position read back from
+        `pos_dev`, row `pos` of the whole tables and the cache's own mask.  Either way 1 <= pos < max_len."""
+        pos = self.length
+        if self.replay:
+            pos = int(self.pos_dev.item())
+            if key_valid is not None:
+                raise ValueError("StaticKVCache.%s: in replay mode the mask is the cache's own (`valid`); pass key_valid=None" % who)
+            key_valid = self.valid
+            if cos is not None:
+                if cos.dim() != 2 or cos.shape[0] < self.max_len:
+                    raise ValueError("StaticKVCache: replay mode takes the whole cos / sin tables [>= max_len, %s]" % width)
+                if 0 <= pos < cos.shape[0]:
+                    cos, sin = cos[pos], sin[pos]
+        if pos < 1 or pos >= self.max_len:
+            raise ValueError("StaticKVCache: a cached step needs 1 <= length < max_len (length=%d, max_len=%d)" % (pos, self.max_len))
+        return pos, cos, sin, key_valid
+
+    def _attend_appended(self, layer: int, qf, pos: int, scale: float, key_valid, slopes, out_dtype) -> torch.Tensor:
+        """The tail of both restatements, slot `pos` written: qf [N,H,d] (rotated, in fp32 at least) over keys 0..pos gathered through the
+        table (int8: dequantised), grouped heads repeated, ALiBi, padding mask, a fully masked row -> 0.  Returns o [N, H*d] in out_dtype."""
+        (N, H, d), ct = qf.shape, qf.dtype
+        k, v = self._gathered(self.k[layer], pos + 1), self._gathered(self.v[layer], pos + 1)     # column pos of the table is the row's own index
+        if self.int8:
+            k = dequantize_kv_int8(k, self._gathered(self.k_scale[layer], pos + 1), ct)
+            v = dequantize_kv_int8(v, self._gathered(self.v_scale[layer], pos + 1), ct)
+        else:
+            k, v = k.to(ct), v.to(ct)
         if k.shape[1] != H:
             k, v = k.repeat_interleave(H // k.shape[1], dim=1), v.repeat_interleave(H // v.shape[1], dim=1)
         s_ = torch.einsum("nhd,nhjd->nhj", qf * scale, k)
         if slopes is not None:
-            s_ = s_ + slopes.to(ct).view(1, H, 1) * torch.arange(-pos, 1, device=q.device, dtype=ct).view(1, 1, -1)
+            s_ = s_ + slopes.to(ct).view(1, H, 1) * torch.arange(-pos, 1, device=qf.device, dtype=ct).view(1, 1, -1)
         dead = None
         if key_valid is not None:
             ok = key_valid[:, :pos + 1].bool()
@@ -366,7 +388,7 @@ class StaticKVCache:
         o = torch.einsum("nhj,nhjd->nhd", torch.softmax(s_, dim=-1), v)
         if dead is not None:
             o = o.masked_fill(dead[:, None, None], 0.0)
-        return o.reshape(N, H * d).to(q.dtype)
+        return o.reshape(N, H * d).to(out_dtype)
 
     # ---- the cached step of the Persimmon host (OtterHD / Fuyu-8B): q / k LayerNorm per head + partial rotary fused into the step ---------
 
@@ -405,20 +427,10 @@ class StaticKVCache:
         position back to the host: it cannot be captured).  The same deliberate exception to "no PyTorch path" as `attend_reference`."""
         if self.int8:
             raise NotImplementedError("StaticKVCache.attend_persimmon: an int8 key / value cache is not built for head_dim 64 (the Persimmon host)")
-        pos, N, H, d = self.length, qkv.shape[0], qkv.shape[1], qkv.shape[3]
         if self.replay:
             self.kernel_steps = False
-            pos = int(self.pos_dev.item())
-            if key_valid is not None:
-                raise ValueError("StaticKVCache.attend_persimmon_reference: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
-            key_valid = self.valid
-            if cos.dim() != 2 or cos.shape[0] < self.max_len:
-                raise ValueError("StaticKVCache: replay mode takes the whole cos / sin tables [>= max_len, rot]")
-            if 0 <= pos < cos.shape[0]:
-                cos, sin = cos[pos], sin[pos]
-        if pos < 1 or pos >= self.max_len:
-            raise ValueError("StaticKVCache: a cached step needs 1 <= length < max_len (length=%d, max_len=%d)" % (pos, self.max_len))
-        ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+        pos, cos, sin, key_valid = self._step_inputs("attend_persimmon_reference", "rot", cos, sin, key_valid)
+        d, ct = qkv.shape[3], torch.float64 if qkv.dtype == torch.float64 else torch.float32
         qf, kf, v_new = qkv[:, :, 0].to(ct), qkv[:, :, 1].to(ct), qkv[:, :, 2]
         if gq is not None:
             qf = torch.nn.functional.layer_norm(qf, (d,), gq.to(ct), bq.to(ct), eps)
@@ -429,17 +441,4 @@ class StaticKVCache:
         qf = qf.to(qkv.dtype).to(ct)                                           # (the kernel rounds q' to the compute dtype, then scales)
         self.k[layer, :, :, pos] = kf.to(self.dtype)
         self.v[layer, :, :, pos] = v_new.to(self.dtype)
-        k = self._gathered(self.k[layer], pos + 1).to(ct)                      # column pos of the table is the row's own index
-        v = self._gathered(self.v[layer], pos + 1).to(ct)
-        s_ = torch.einsum("nhd,nhjd->nhj", qf * scale, k)
-        dead = None
-        if key_valid is not None:
-            ok = key_valid[:, :pos + 1].bool()
-            s_ = s_.masked_fill(~ok[:, None, :], float("-inf"))
-            dead = ~ok.any(dim=1)
-            if bool(dead.any()):
-                s_ = s_.masked_fill(dead[:, None, None], 0.0)
-        o = torch.einsum("nhj,nhjd->nhd", torch.softmax(s_, dim=-1), v)
-        if dead is not None:
-            o = o.masked_fill(dead[:, None, None], 0.0)
-        return o.reshape(N, H * d).to(qkv.dtype)
+        return self._attend_appended(layer, qf, pos, scale, key_valid, None, qkv.dtype)

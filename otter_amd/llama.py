@@ -308,31 +308,23 @@ class LlamaModel(LlamaPreTrainedModel):
                 cache.fill(i, k, v)                          # legacy layout: k, v [B,H,S,d]
             cache.length = S
             return BaseModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=cache)
+        key_valid = None
         if cache.replay:
             # replay mode (kv_cache.py): the position, the mask and the beam table are the cache's own device buffers and the kernel takes
             # its rotary row from the whole table (built to the cache's capacity on the first such step, before any capture) -- nothing
-            # below depends on the position, so this branch can be captured once and replayed (generate(..., graph_decode=True))
+            # here depends on the position, so the step can be captured once and replayed (generate(..., graph_decode=True))
             if position_ids is not None:
                 raise ValueError("LlamaModel: custom position_ids cannot follow a StaticKVCache in replay mode (the position is the cache's own)")
-            cos_t, sin_t = self.rotary_emb.tables(cache.max_len, x.device)
-            delta = None
-            for i, layer in enumerate(self.layers):
-                if delta is not None and getattr(layer, "gated_cross_attn_layer", None) is not None:
-                    x = x + delta
-                    delta = None
-                x, _, delta = layer(x, cos=cos_t, sin=sin_t, key_valid=None, deferred=delta, defer_out=True, static=(cache, i))
-            _, x = self.norm(x, delta=delta, out_dtype=OF.compute_dtype_for(x))
-            cache.advance()
-            return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
-        pos = cache.length
-        cos_t, sin_t = self.rotary_emb.tables(pos + 1, x.device)
-        if position_ids is None:
-            cos, sin = cos_t[pos:pos + 1], sin_t[pos:pos + 1]
+            cos, sin = self.rotary_emb.tables(cache.max_len, x.device)
         else:
-            cos, sin = cos_t[position_ids], sin_t[position_ids]                  # [B,1,d]
-        key_valid = None
-        if attention_mask is not None:                       # (no host round trip: the kernel evaluates the mask, all-valid or not)
-            key_valid = attention_mask[:, -(pos + 1):].to(torch.uint8)
+            pos = cache.length
+            cos_t, sin_t = self.rotary_emb.tables(pos + 1, x.device)
+            if position_ids is None:
+                cos, sin = cos_t[pos:pos + 1], sin_t[pos:pos + 1]
+            else:
+                cos, sin = cos_t[position_ids], sin_t[position_ids]                  # [B,1,d]
+            if attention_mask is not None:                   # (no host round trip: the kernel evaluates the mask, all-valid or not)
+                key_valid = attention_mask[:, -(pos + 1):].to(torch.uint8)
         delta = None
         for i, layer in enumerate(self.layers):
             if delta is not None and getattr(layer, "gated_cross_attn_layer", None) is not None:
@@ -340,7 +332,7 @@ class LlamaModel(LlamaPreTrainedModel):
                 delta = None
             x, _, delta = layer(x, cos=cos, sin=sin, key_valid=key_valid, deferred=delta, defer_out=True, static=(cache, i))
         _, x = self.norm(x, delta=delta, out_dtype=OF.compute_dtype_for(x))
-        cache.length = pos + 1
+        cache.end_step()
         return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,

@@ -401,12 +401,15 @@ class MPTModel(MPTPreTrainedModel):
     def set_input_embeddings(self, value):
         self.wte = value
 
-    def _attn_bias(self, s_k: int, device, attention_mask: Optional[torch.Tensor]):
-        """[1 or B, H, 1, s_k] fp32 = ALiBi (key-position form, attention.py:458-464) + padding (modeling_mpt.py:135-144)."""
+    def _alibi_slopes(self, device) -> torch.Tensor:
         if self._slopes is None or self._slopes.device != device:
             self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(device)
+        return self._slopes
+
+    def _attn_bias(self, s_k: int, device, attention_mask: Optional[torch.Tensor]):
+        """[1 or B, H, 1, s_k] fp32 = ALiBi (key-position form, attention.py:458-464) + padding (modeling_mpt.py:135-144)."""
         pos = torch.arange(1 - s_k, 1, dtype=torch.float32, device=device)
-        bias = pos.view(1, 1, 1, s_k) * self._slopes.view(1, -1, 1, 1)
+        bias = pos.view(1, 1, 1, s_k) * self._alibi_slopes(device).view(1, -1, 1, 1)
         if attention_mask is not None:
             am = attention_mask.bool()[:, -s_k:]
             if not bool(am.all()):
@@ -431,9 +434,7 @@ class MPTModel(MPTPreTrainedModel):
                 if not bool(am[:, 0].all()) and torch.is_grad_enabled():
                     return None
                 key_valid = am.to(torch.uint8).contiguous()
-        if self._slopes is None or self._slopes.device != x.device:
-            self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
-        return self._slopes.float().contiguous(), key_valid
+        return self._alibi_slopes(x.device).float().contiguous(), key_valid
 
     def _decode_spec(self, x, S, s_past, attention_mask):
         """(alibi slopes, key_valid or None) when the HIP decode kernel covers this call: one new token over a non-empty cache,
@@ -448,9 +449,7 @@ class MPTModel(MPTPreTrainedModel):
             am = attention_mask.bool()[:, -(s_past + 1):]
             if not bool(am.all()):
                 key_valid = am.to(torch.uint8).contiguous()
-        if self._slopes is None or self._slopes.device != x.device:
-            self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
-        return self._slopes.float().contiguous(), key_valid
+        return self._alibi_slopes(x.device).float().contiguous(), key_valid
 
     def _forward_static(self, input_ids, cache: StaticKVCache, attention_mask):
         """`past_key_values` is a StaticKVCache.  Empty: the prompt pass is the ordinary one (flash or SDPA), whose keys / values are copied
@@ -465,29 +464,13 @@ class MPTModel(MPTPreTrainedModel):
             cache.length = S
             return BaseModelOutputWithPast(last_hidden_state=out.last_hidden_state, past_key_values=cache)
         x = self.wte(input_ids)
-        if cache.replay:
-            # replay mode (kv_cache.py): the position, the mask and the table are the cache's own device buffers -- nothing below depends
-            # on the position, so this branch can be captured once and replayed (generate(..., graph_decode=True))
-            if self._slopes is None or self._slopes.device != x.device:
-                self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
-            slopes = self._slopes.float().contiguous()
-            delta = None
-            for i, block in enumerate(self.blocks):
-                if delta is not None and getattr(block, "gated_cross_attn_layer", None) is not None and not _gated_takes_deferred(block, x, delta):
-                    x = x + delta
-                    delta = None
-                out = block(x, deferred=delta, defer_out=True, static=(cache, i, slopes, None))
-                x, delta = out[0], out[3]
-            _, x = self.norm_f.add_forward(x, delta)
-            cache.advance()
-            return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
-        pos = cache.length
-        if self._slopes is None or self._slopes.device != x.device:
-            self._slopes = alibi_slopes(self.config.n_heads, self.alibi_bias_max).to(x.device)
-        slopes = self._slopes.float().contiguous()          # (fp32 and contiguous already: no copy)
+        slopes = self._alibi_slopes(x.device).float().contiguous()          # (fp32 and contiguous already: no copy)
+        # replay mode (kv_cache.py): the position, the mask and the table are the cache's own device buffers -- nothing here depends on the
+        # position, so the step can be captured once and replayed (generate(..., graph_decode=True)).  Otherwise the mask goes to the kernel as
+        # it is (no host round trip: the kernel evaluates it, all-valid or not)
         key_valid = None
-        if attention_mask is not None:                       # (no host round trip: the kernel evaluates the mask, all-valid or not)
-            key_valid = attention_mask[:, -(pos + 1):].to(torch.uint8)
+        if not cache.replay and attention_mask is not None:
+            key_valid = attention_mask[:, -(cache.length + 1):].to(torch.uint8)
         delta = None
         for i, block in enumerate(self.blocks):
             if delta is not None and getattr(block, "gated_cross_attn_layer", None) is not None and not _gated_takes_deferred(block, x, delta):
@@ -496,7 +479,7 @@ class MPTModel(MPTPreTrainedModel):
             out = block(x, deferred=delta, defer_out=True, static=(cache, i, slopes, key_valid))
             x, delta = out[0], out[3]
         _, x = self.norm_f.add_forward(x, delta)
-        cache.length = pos + 1
+        cache.end_step()
         return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
 
     def forward(self, input_ids, past_key_values=None, attention_mask=None, use_cache=None, return_dict=True, **unused):

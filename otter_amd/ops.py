@@ -492,16 +492,154 @@ def decode_attn(q, k, v, slopes, key_valid, scale):
 
 
 PERSIMMON_DECODE_MAX_KEYS = 65536      # include/otter_hip.h: S_past + 1 <= 65536
+DECODE_CACHED_MAX_KEYS = 65536        # include/otter_hip.h: S_max <= 65536
 
 
 def persimmon_decode_workspace_bytes(B: int, H: int, Sk: int) -> int:
-    """OTTER_PERSIMMON_DECODE_WORKSPACE_BYTES of include/otter_hip.h."""
+    """OTTER_PERSIMMON_DECODE_WORKSPACE_BYTES of include/otter_hip.h; its _CACHED (Sk = pos + 1) and _CACHED_DYN (Sk = S_max) forms are the same."""
     return B * H * ((Sk + 127) // 128) * 66 * 4
 
+
+persimmon_decode_cached_workspace_bytes = persimmon_decode_cached_dyn_workspace_bytes = persimmon_decode_workspace_bytes
+
+
+def decode_attn_cached_workspace_bytes(N: int, H: int, Sk: int) -> int:
+    """OTTER_DECODE_CACHED_WORKSPACE_BYTES of include/otter_hip.h (Sk = pos + 1); its _DYN (Sk = S_max), _I8 and _I8_DYN forms are the same."""
+    return N * H * ((Sk + 127) // 128) * 130 * 4
+
+
+decode_attn_cached_dyn_workspace_bytes = decode_attn_cached_i8_workspace_bytes = decode_attn_cached_i8_dyn_workspace_bytes = \
+    decode_attn_cached_workspace_bytes
+
+
+# ---- the argument checks of the cached-decode entry points -------------------------------------------------------------------------------
+# One checker per kind of argument; each takes the entry point's name (the prefix of its messages) and whatever varies between entry points.
+# They look at dtype, shape, strides and alignment only, so they run on CPU tensors: tests/test_decode_bindings_cpu.py holds every message,
+# the order of the checks and every argument tuple to a recording.  DESIGN.md 4.9 lists what differs between entry points on purpose.
 
 def _decode_past_ok(t, B, H, S_past) -> bool:
     return (t.dtype == torch.bfloat16 and t.dim() == 4 and tuple(t.shape) == (B, H, S_past, 64) and t.stride(3) == 1
             and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.stride(2) % 8 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _check_new_128(name, q, k_new, v_new):
+    """The new token at head_dim 128, three views; returns (N, H)."""
+    if q.dim() != 3:
+        raise K.OtterHipError(f"{name}: q must be [N,H,128]")
+    N, H = q.shape[:2]
+    for t in (q, k_new, v_new):
+        if (t.dtype != torch.bfloat16 or t.dim() != 3 or tuple(t.shape) != (N, H, 128) or (st := t.stride())[2] != 1 or st[0] % 8 or st[1] % 8
+                or t.data_ptr() % 16):
+            raise K.OtterHipError(f"{name}: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
+    return N, H
+
+
+def _check_qkv_64(name, qkv):
+    """The new token at head_dim 64, one fused tensor; returns (N, H)."""
+    if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[2:] != (3, 64) or not qkv.is_contiguous() or qkv.data_ptr() % 16:
+        raise K.OtterHipError(f"{name}: qkv must be contiguous bf16 [N,H,3,64], 16-B aligned")
+    return qkv.shape[:2]
+
+
+def _check_caches(name, k_cache, v_cache, N, H, dtype, hd, mod):
+    """The static cache pair: `dtype` [N,H,S_max,hd], row and head strides % mod (8 elements of bf16, 16 of int8: 16 bytes); returns S_max."""
+    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
+    for t in (k_cache, v_cache):
+        if (t.dtype != dtype or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, hd) or (st := t.stride())[3] != 1 or st[2] != hd
+                or st[0] % mod or st[1] % mod or st[1] < S_max * hd or t.data_ptr() % 16):
+            raise K.OtterHipError(f"{name}: k_cache / v_cache must be {'int8' if dtype == torch.int8 else 'bf16'} [N,H,S_max,{hd}] "
+                                  f"with key stride {hd}, unit dim stride, 16-B aligned")
+    return S_max
+
+
+def _check_scales(name, k_scale, v_scale, N, H, S_max):
+    for t in (k_scale, v_scale):
+        if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape) != (N, H, S_max) or t.stride(2) != 1 or t.stride(1) < S_max:
+            raise K.OtterHipError(f"{name}: k_scale / v_scale must be fp32 [N,H,S_max] with a unit key stride")
+
+
+def _check_s_max(name, S_max, limit):
+    if S_max < 2 or S_max > limit:
+        raise K.OtterHipError(f"{name}: S_max={S_max} outside [2, {limit}]")
+
+
+def _check_pos(name, pos, S_max, limit=None):
+    """The position scalar; returns it as an int.  `limit`: the upper limit of S_max is part of this check and of its message (the head_dim-128
+    entry points, which have no S_max check of their own)."""
+    pos = int(pos)
+    if (limit is not None and S_max > limit) or pos < 1 or pos >= S_max:
+        raise K.OtterHipError(f"{name}: pos={pos} outside [1, S_max) with S_max={S_max}" + (f" (limit {limit})" if limit is not None else ""))
+    return pos
+
+
+def _check_pos_dev(name, pos_dev):
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
+        raise K.OtterHipError(f"{name}: pos_dev must be an int32 tensor of one element")
+
+
+def _check_norm_rot(name, gq, bq, gk, bk, rot):
+    for t in (gq, bq, gk, bk):
+        if t.dtype != torch.float32 or t.numel() != 64 or not t.is_contiguous():
+            raise K.OtterHipError(f"{name}: gamma / beta must be contiguous fp32 [64]")
+    if rot <= 0 or rot > 64 or rot % 16:
+        raise K.OtterHipError(f"{name}: rot={rot} must be a multiple of 16 in (0, 64]")
+
+
+def _check_rotary_rows_64(name, cos_row, sin_row, rot):
+    for t in (cos_row, sin_row):
+        if t.dtype != torch.float32 or t.numel() != rot or not t.is_contiguous():
+            raise K.OtterHipError(f"{name}: cos_row / sin_row must be contiguous fp32 [rot]")
+
+
+def _check_rotary_rows_128(name, cos, sin, N):
+    """Both or neither; [128] (one row for all) or [N,128].  Returns the row stride handed to the library (0: one row, or no rotary)."""
+    if (cos is None) != (sin is None):
+        raise K.OtterHipError(f"{name}: cos and sin must both be given or both be None")
+    if cos is None:
+        return 0
+    for t in (cos, sin):
+        if (t.dtype != torch.float32 or t.shape[-1] != 128 or t.stride(-1) != 1 or tuple(t.shape) not in ((128,), (N, 128))
+                or tuple(t.shape) != tuple(cos.shape) or t.stride() != cos.stride()):
+            raise K.OtterHipError(f"{name}: cos / sin must be fp32 [128] or [N,128] with a unit dim stride and equal strides")
+    return cos.stride(0) if cos.dim() == 2 else 0
+
+
+def _check_rotary_tables(name, cos_table, sin_table, S_max, width, width_text, optional):
+    """fp32 [>= S_max, width] with equal strides; `optional`: both may be None (head_dim 128).  Returns the row stride (0: no rotary)."""
+    if optional:
+        if (cos_table is None) != (sin_table is None):
+            raise K.OtterHipError(f"{name}: cos_table and sin_table must both be given or both be None")
+        if cos_table is None:
+            return 0
+    for t in (cos_table, sin_table):
+        if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != width or t.stride(1) != 1 or t.stride(0) < width
+                or t.stride() != cos_table.stride()):
+            raise K.OtterHipError(f"{name}: cos_table / sin_table must be fp32 [>= S_max, {width_text}] with a unit dim stride and equal strides")
+    return cos_table.stride(0)
+
+
+def _check_rows(name, t, what, dtype, N, need, need_text, strict):
+    """src (int32) or key_valid (uint8): [N, >= need] or None.  Returns the row stride handed to the library (0 for None).  `strict`: a row
+    stride below `need` is refused here when N > 1 and raised to `need` when N == 1; otherwise it is passed as it is and the library decides."""
+    if t is None:
+        return 0
+    if (t.dtype != dtype or t.dim() != 2 or t.shape[0] != N or t.shape[1] < need or t.stride(1) != 1
+            or (strict and N > 1 and t.stride(0) < need)):
+        raise K.OtterHipError(f"{name}: {what} must be {str(dtype)[6:]} [N, >= {need_text}] with a unit column stride")
+    return max(t.stride(0), need) if strict else t.stride(0)
+
+
+def _check_slopes(name, slopes, H):
+    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
+        raise K.OtterHipError(f"{name}: slopes must be contiguous fp32 [H]")
+
+
+def _out_or_new(name, out, N, H, hd, device):
+    if out is None:
+        return torch.empty((N, H * hd), dtype=torch.bfloat16, device=device)
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * hd) or not out.is_contiguous():
+        raise K.OtterHipError(f"{name}: out must be a contiguous bf16 [N, H*{hd}] tensor")
+    return out
 
 
 def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past, key_valid, rot, eps, scale):
@@ -510,6 +648,13 @@ def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past,
     unit dim stride and strides that are multiples of 8 (read only); key_valid uint8 [B,S_past+1] or None.
     Returns (o [B,H*64], k_new [B,H,S_past+1,64], v_new [B,H,S_past+1,64]), all bf16 and freshly allocated."""
     K.require_cuda(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past, key_valid)
+    args, ret = _persimmon_decode_args(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past, key_valid, rot, eps, scale)
+    K.check(K.lib().otter_persimmon_decode_attn(*args, K.stream()), "persimmon_decode_attn")
+    return ret
+
+
+def _persimmon_decode_args(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past, key_valid, rot, eps, scale):
+    name = "persimmon_decode_attn"
     if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[2:] != (3, 64) or not qkv.is_contiguous():
         raise K.OtterHipError("persimmon_decode_attn: qkv must be contiguous bf16 [B,H,3,64]")
     B, H = qkv.shape[:2]
@@ -518,59 +663,44 @@ def persimmon_decode_attn(qkv, gq, bq, gk, bk, cos_row, sin_row, k_past, v_past,
         raise K.OtterHipError(f"persimmon_decode_attn: past length {S_past} outside [1, {PERSIMMON_DECODE_MAX_KEYS - 1}]")
     if not _decode_past_ok(k_past, B, H, S_past) or not _decode_past_ok(v_past, B, H, S_past):
         raise K.OtterHipError("persimmon_decode_attn: k_past / v_past must be bf16 [B,H,S_past,64], unit dim stride, strides % 8 == 0, 16-B aligned")
-    for t in (gq, bq, gk, bk):
-        if t.dtype != torch.float32 or t.numel() != 64 or not t.is_contiguous():
-            raise K.OtterHipError("persimmon_decode_attn: gamma / beta must be contiguous fp32 [64]")
-    if rot <= 0 or rot > 64 or rot % 16:
-        raise K.OtterHipError(f"persimmon_decode_attn: rot={rot} must be a multiple of 16 in (0, 64]")
-    for t in (cos_row, sin_row):
-        if t.dtype != torch.float32 or t.numel() != rot or not t.is_contiguous():
-            raise K.OtterHipError("persimmon_decode_attn: cos_row / sin_row must be contiguous fp32 [rot]")
+    _check_norm_rot(name, gq, bq, gk, bk, rot)
+    _check_rotary_rows_64(name, cos_row, sin_row, rot)
     Sk = S_past + 1
     if key_valid is not None and (key_valid.dtype != torch.uint8 or not key_valid.is_contiguous() or tuple(key_valid.shape) != (B, Sk)):
         raise K.OtterHipError("persimmon_decode_attn: key_valid must be contiguous uint8 [B,S_past+1]")
     k_new = torch.empty((B, H, Sk, 64), dtype=torch.bfloat16, device=qkv.device)
     v_new = torch.empty_like(k_new)
     o = torch.empty((B, H * 64), dtype=torch.bfloat16, device=qkv.device)
-    nbytes = persimmon_decode_workspace_bytes(B, H, Sk)
-    ws = _ws.get(nbytes, qkv.device)
-    K.check(K.lib().otter_persimmon_decode_attn(qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_row.data_ptr(),
-                                                sin_row.data_ptr(), k_past.data_ptr(), k_past.stride(0), k_past.stride(1), k_past.stride(2),
-                                                k_past.stride(3), v_past.data_ptr(), v_past.stride(0), v_past.stride(1), v_past.stride(2),
-                                                v_past.stride(3), K.ptr(key_valid), k_new.data_ptr(), v_new.data_ptr(), o.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), B, H, S_past, 64, int(rot), float(eps), float(scale), K.stream()),
-            "persimmon_decode_attn")
-    return o, k_new, v_new
+    ws = _ws.get(persimmon_decode_workspace_bytes(B, H, Sk), qkv.device)
+    return (qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_row.data_ptr(), sin_row.data_ptr(),
+            k_past.data_ptr(), k_past.stride(0), k_past.stride(1), k_past.stride(2), k_past.stride(3), v_past.data_ptr(), v_past.stride(0),
+            v_past.stride(1), v_past.stride(2), v_past.stride(3), K.ptr(key_valid), k_new.data_ptr(), v_new.data_ptr(), o.data_ptr(),
+            ws.data_ptr(), ws.numel(), B, H, S_past, 64, int(rot), float(eps), float(scale)), (o, k_new, v_new)
 
 
-def persimmon_decode_cached_workspace_bytes(N: int, H: int, Sk: int) -> int:
-    """OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES of include/otter_hip.h."""
-    return N * H * ((Sk + 127) // 128) * 66 * 4
-
-
-def persimmon_decode_cached_dyn_workspace_bytes(N: int, H: int, S_max: int) -> int:
-    """OTTER_PERSIMMON_DECODE_CACHED_DYN_WORKSPACE_BYTES of include/otter_hip.h."""
-    return N * H * ((S_max + 127) // 128) * 66 * 4
-
-
-def _persimmon_cached_common(name, qkv, gq, bq, gk, bk, k_cache, v_cache, rot):
-    """The checks the two static-cache entry points share; returns (N, H, S_max)."""
-    if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[2:] != (3, 64) or not qkv.is_contiguous() or qkv.data_ptr() % 16:
-        raise K.OtterHipError(f"{name}: qkv must be contiguous bf16 [N,H,3,64], 16-B aligned")
-    N, H = qkv.shape[:2]
-    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
-    for t in (k_cache, v_cache):
-        if (t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 64) or t.stride(3) != 1 or t.stride(2) != 64
-                or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < S_max * 64 or t.data_ptr() % 16):
-            raise K.OtterHipError(f"{name}: k_cache / v_cache must be bf16 [N,H,S_max,64] with key stride 64, unit dim stride, 16-B aligned")
-    if S_max < 2 or S_max > PERSIMMON_DECODE_MAX_KEYS:
-        raise K.OtterHipError(f"{name}: S_max={S_max} outside [2, {PERSIMMON_DECODE_MAX_KEYS}]")
-    for t in (gq, bq, gk, bk):
-        if t.dtype != torch.float32 or t.numel() != 64 or not t.is_contiguous():
-            raise K.OtterHipError(f"{name}: gamma / beta must be contiguous fp32 [64]")
-    if rot <= 0 or rot > 64 or rot % 16:
-        raise K.OtterHipError(f"{name}: rot={rot} must be a multiple of 16 in (0, 64]")
-    return N, H, S_max
+def _persimmon_cached_args(name, dyn, qkv, gq, bq, gk, bk, cos, sin, k_cache, v_cache, pos, rot, eps, scale, src, key_valid, out):
+    """The two static-cache entry points at head_dim 64, from tensors to (the library's arguments up to the stream, o) or an OtterHipError.
+    `dyn`: `pos` is pos_dev, cos / sin are the tables, and src / key_valid must cover every position."""
+    N, H = _check_qkv_64(name, qkv)
+    S_max = _check_caches(name, k_cache, v_cache, N, H, torch.bfloat16, 64, 8)
+    _check_s_max(name, S_max, PERSIMMON_DECODE_MAX_KEYS)
+    _check_norm_rot(name, gq, bq, gk, bk, rot)
+    if dyn:
+        _check_pos_dev(name, pos)
+        rotary = (cos.data_ptr(), sin.data_ptr(), _check_rotary_tables(name, cos, sin, S_max, rot, "rot", False))
+        keys, pos = S_max, pos.data_ptr()
+    else:
+        keys = pos = _check_pos(name, pos, S_max)
+        keys += 1
+        _check_rotary_rows_64(name, cos, sin, rot)
+        rotary = (cos.data_ptr(), sin.data_ptr())
+    src_rs = _check_rows(name, src, "src", torch.int32, N, keys - 1, "S_max - 1" if dyn else "pos", True)
+    kv_rs = _check_rows(name, key_valid, "key_valid", torch.uint8, N, keys, "S_max" if dyn else "pos+1", True)
+    o = _out_or_new(name, out, N, H, 64, qkv.device)
+    ws = _ws.get(persimmon_decode_cached_workspace_bytes(N, H, keys), qkv.device)
+    return (qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), *rotary, k_cache.data_ptr(), k_cache.stride(0),
+            k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), K.ptr(src), src_rs, K.ptr(key_valid), kv_rs,
+            o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 64, int(rot), float(eps), float(scale)), o
 
 
 def persimmon_decode_attn_cached(qkv, gq, bq, gk, bk, cos_row, sin_row, k_cache, v_cache, pos, rot, eps, scale, src=None, key_valid=None):
@@ -579,27 +709,9 @@ def persimmon_decode_attn_cached(qkv, gq, bq, gk, bk, cos_row, sin_row, k_cache,
     place at slot `pos` (1 <= pos < S_max) of every row; src int32 [N, >= pos] (row stride free) or None; key_valid uint8 [N, >= pos+1] or
     None.  Returns o [N,H*64] bf16."""
     K.require_cuda(qkv, gq, bq, gk, bk, cos_row, sin_row, k_cache, v_cache, src, key_valid)
-    N, H, S_max = _persimmon_cached_common("persimmon_decode_attn_cached", qkv, gq, bq, gk, bk, k_cache, v_cache, rot)
-    pos = int(pos)
-    if pos < 1 or pos >= S_max:
-        raise K.OtterHipError(f"persimmon_decode_attn_cached: pos={pos} outside [1, S_max) with S_max={S_max}")
-    for t in (cos_row, sin_row):
-        if t.dtype != torch.float32 or t.numel() != rot or not t.is_contiguous():
-            raise K.OtterHipError("persimmon_decode_attn_cached: cos_row / sin_row must be contiguous fp32 [rot]")
-    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < pos or src.stride(1) != 1
-                            or (N > 1 and src.stride(0) < pos)):
-        raise K.OtterHipError("persimmon_decode_attn_cached: src must be int32 [N, >= pos] with a unit column stride")
-    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < pos + 1
-                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < pos + 1)):
-        raise K.OtterHipError("persimmon_decode_attn_cached: key_valid must be uint8 [N, >= pos+1] with a unit column stride")
-    o = torch.empty((N, H * 64), dtype=torch.bfloat16, device=qkv.device)
-    ws = _ws.get(persimmon_decode_cached_workspace_bytes(N, H, pos + 1), qkv.device)
-    K.check(K.lib().otter_persimmon_decode_attn_cached(
-        qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_row.data_ptr(), sin_row.data_ptr(), k_cache.data_ptr(),
-        k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), K.ptr(src),
-        max(src.stride(0), pos) if src is not None else 0, K.ptr(key_valid), max(key_valid.stride(0), pos + 1) if key_valid is not None else 0,
-        o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 64, int(rot), float(eps), float(scale), K.stream()),
-        "persimmon_decode_attn_cached")
+    args, o = _persimmon_cached_args("persimmon_decode_attn_cached", False, qkv, gq, bq, gk, bk, cos_row, sin_row, k_cache, v_cache, pos, rot,
+                                     eps, scale, src, key_valid, None)
+    K.check(K.lib().otter_persimmon_decode_attn_cached(*args, K.stream()), "persimmon_decode_attn_cached")
     return o
 
 
@@ -610,47 +722,44 @@ def persimmon_decode_attn_cached_dyn(qkv, gq, bq, gk, bk, cos_table, sin_table, 
     takes row pos); src int32 [N, >= S_max - 1]; key_valid uint8 [N, >= S_max].  No argument of the launch depends on the position: the same
     call, captured in a graph, serves every step.  Returns o [N,H*64] bf16 (`out`: a contiguous bf16 [N,H*64] tensor to write instead)."""
     K.require_cuda(qkv, gq, bq, gk, bk, cos_table, sin_table, k_cache, v_cache, pos_dev, src, key_valid, out)
-    N, H, S_max = _persimmon_cached_common("persimmon_decode_attn_cached_dyn", qkv, gq, bq, gk, bk, k_cache, v_cache, rot)
-    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
-        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: pos_dev must be an int32 tensor of one element")
-    for t in (cos_table, sin_table):
-        if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != rot or t.stride(1) != 1 or t.stride(0) < rot
-                or t.stride() != cos_table.stride()):
-            raise K.OtterHipError("persimmon_decode_attn_cached_dyn: cos_table / sin_table must be fp32 [>= S_max, rot] with a unit dim stride "
-                                  "and equal strides")
-    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < S_max - 1 or src.stride(1) != 1
-                            or (N > 1 and src.stride(0) < S_max - 1)):
-        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: src must be int32 [N, >= S_max - 1] with a unit column stride")
-    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < S_max
-                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < S_max)):
-        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: key_valid must be uint8 [N, >= S_max] with a unit column stride")
-    if out is None:
-        o = torch.empty((N, H * 64), dtype=torch.bfloat16, device=qkv.device)
-    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * 64) or not out.is_contiguous():
-        raise K.OtterHipError("persimmon_decode_attn_cached_dyn: out must be a contiguous bf16 [N, H*64] tensor")
-    else:
-        o = out
-    ws = _ws.get(persimmon_decode_cached_dyn_workspace_bytes(N, H, S_max), qkv.device)
-    K.check(K.lib().otter_persimmon_decode_attn_cached_dyn(
-        qkv.data_ptr(), gq.data_ptr(), bq.data_ptr(), gk.data_ptr(), bk.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(),
-        cos_table.stride(0), k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1),
-        K.ptr(src), max(src.stride(0), S_max - 1) if src is not None else 0, K.ptr(key_valid),
-        max(key_valid.stride(0), S_max) if key_valid is not None else 0, o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos_dev.data_ptr(),
-        S_max, 64, int(rot), float(eps), float(scale), K.stream()), "persimmon_decode_attn_cached_dyn")
+    args, o = _persimmon_cached_args("persimmon_decode_attn_cached_dyn", True, qkv, gq, bq, gk, bk, cos_table, sin_table, k_cache, v_cache,
+                                     pos_dev, rot, eps, scale, src, key_valid, out)
+    K.check(K.lib().otter_persimmon_decode_attn_cached_dyn(*args, K.stream()), "persimmon_decode_attn_cached_dyn")
     return o
 
 
-DECODE_CACHED_MAX_KEYS = 65536        # include/otter_hip.h: S_max <= 65536
-
-
-def decode_attn_cached_workspace_bytes(N: int, H: int, Sk: int) -> int:
-    """OTTER_DECODE_CACHED_WORKSPACE_BYTES of include/otter_hip.h."""
-    return N * H * ((Sk + 127) // 128) * 130 * 4
-
-
-def _decode_new_ok(t, N, H) -> bool:
-    return (t.dtype == torch.bfloat16 and t.dim() == 3 and tuple(t.shape) == (N, H, 128) and t.stride(2) == 1 and t.stride(0) % 8 == 0
-            and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0)
+def _decode_cached_args(name, dyn, q, k_new, v_new, k_cache, v_cache, scales, pos, scale, cos, sin, src, key_valid, slopes, out):
+    """The four static-cache entry points at head_dim 128, from tensors to (the library's arguments up to the stream, o) or an OtterHipError.
+    `scales`: (k_scale, v_scale) of an int8 cache, None for a bf16 one; `dyn`: `pos` is pos_dev, cos / sin are the tables, src / key_valid
+    must cover every position and their row stride is checked here (the position-scalar forms leave it to the library)."""
+    i8 = scales is not None
+    N, H = _check_new_128(name, q, k_new, v_new)
+    S_max = _check_caches(name, k_cache, v_cache, N, H, torch.int8 if i8 else torch.bfloat16, 128, 16 if i8 else 8)
+    if i8:
+        _check_scales(name, scales[0], scales[1], N, H, S_max)
+        _check_slopes(name, slopes, H)                  # (the bf16 entry points check slopes after key_valid)
+    if dyn:
+        _check_s_max(name, S_max, DECODE_CACHED_MAX_KEYS)
+        _check_pos_dev(name, pos)
+        rot_stride = _check_rotary_tables(name, cos, sin, S_max, 128, "128", True)
+        keys, pos = S_max, pos.data_ptr()
+    else:
+        keys = pos = _check_pos(name, pos, S_max, DECODE_CACHED_MAX_KEYS)
+        keys += 1
+        rot_stride = _check_rotary_rows_128(name, cos, sin, N)
+    src_rs = _check_rows(name, src, "src", torch.int32, N, keys - 1, "S_max - 1" if dyn else "pos", dyn)
+    kv_rs = _check_rows(name, key_valid, "key_valid", torch.uint8, N, keys, "S_max" if dyn else "pos+1", dyn)
+    if not i8:
+        _check_slopes(name, slopes, H)
+    o = _out_or_new(name, out, N, H, 128, q.device)
+    ws = _ws.get(decode_attn_cached_workspace_bytes(N, H, keys), q.device)
+    caches = (k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1))
+    if i8:
+        ks, vs = scales
+        caches += (ks.data_ptr(), ks.stride(0), ks.stride(1), vs.data_ptr(), vs.stride(0), vs.stride(1))
+    return (q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
+            v_new.stride(1), K.ptr(cos), K.ptr(sin), rot_stride, *caches, K.ptr(src), src_rs, K.ptr(key_valid), kv_rs, K.ptr(slopes),
+            o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 128, float(scale)), o
 
 
 def decode_attn_cached(q, k_new, v_new, k_cache, v_cache, pos, scale, cos=None, sin=None, src=None, key_valid=None, slopes=None):
@@ -660,49 +769,10 @@ def decode_attn_cached(q, k_new, v_new, k_cache, v_cache, pos, scale, cos=None, 
     rows of position `pos` (both or neither: rotate_half rotary on q and k_new); src int32 [N, >= pos] (row stride free) or None;
     key_valid uint8 [N, >= pos+1] or None; slopes fp32 [H] or None.  Returns o [N,H*128] bf16."""
     K.require_cuda(q, k_new, v_new, k_cache, v_cache, cos, sin, src, key_valid, slopes)
-    if q.dim() != 3:
-        raise K.OtterHipError("decode_attn_cached: q must be [N,H,128]")
-    N, H = q.shape[:2]
-    if not (_decode_new_ok(q, N, H) and _decode_new_ok(k_new, N, H) and _decode_new_ok(v_new, N, H)):
-        raise K.OtterHipError("decode_attn_cached: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
-    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
-    for t in (k_cache, v_cache):
-        if (t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 128) or t.stride(3) != 1 or t.stride(2) != 128
-                or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < S_max * 128 or t.data_ptr() % 16):
-            raise K.OtterHipError("decode_attn_cached: k_cache / v_cache must be bf16 [N,H,S_max,128] with key stride 128, unit dim stride, 16-B aligned")
-    pos = int(pos)
-    if S_max > DECODE_CACHED_MAX_KEYS or pos < 1 or pos >= S_max:
-        raise K.OtterHipError(f"decode_attn_cached: pos={pos} outside [1, S_max) with S_max={S_max} (limit {DECODE_CACHED_MAX_KEYS})")
-    if (cos is None) != (sin is None):
-        raise K.OtterHipError("decode_attn_cached: cos and sin must both be given or both be None")
-    cs_stride = 0
-    if cos is not None:
-        for t in (cos, sin):
-            if (t.dtype != torch.float32 or t.shape[-1] != 128 or t.stride(-1) != 1 or tuple(t.shape) not in ((128,), (N, 128))
-                    or tuple(t.shape) != tuple(cos.shape) or t.stride() != cos.stride()):
-                raise K.OtterHipError("decode_attn_cached: cos / sin must be fp32 [128] or [N,128] with a unit dim stride and equal strides")
-        cs_stride = cos.stride(0) if cos.dim() == 2 else 0
-    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < pos or src.stride(1) != 1):
-        raise K.OtterHipError("decode_attn_cached: src must be int32 [N, >= pos] with a unit column stride")
-    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < pos + 1
-                                  or key_valid.stride(1) != 1):
-        raise K.OtterHipError("decode_attn_cached: key_valid must be uint8 [N, >= pos+1] with a unit column stride")
-    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
-        raise K.OtterHipError("decode_attn_cached: slopes must be contiguous fp32 [H]")
-    o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
-    ws = _ws.get(decode_attn_cached_workspace_bytes(N, H, pos + 1), q.device)
-    K.check(K.lib().otter_decode_attn_cached(
-        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
-        v_new.stride(1), K.ptr(cos), K.ptr(sin), cs_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(),
-        v_cache.stride(0), v_cache.stride(1), K.ptr(src), src.stride(0) if src is not None else 0, K.ptr(key_valid),
-        key_valid.stride(0) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 128,
-        float(scale), K.stream()), "decode_attn_cached")
+    args, o = _decode_cached_args("decode_attn_cached", False, q, k_new, v_new, k_cache, v_cache, None, pos, scale, cos, sin, src, key_valid,
+                                  slopes, None)
+    K.check(K.lib().otter_decode_attn_cached(*args, K.stream()), "decode_attn_cached")
     return o
-
-
-def decode_attn_cached_dyn_workspace_bytes(N: int, H: int, S_max: int) -> int:
-    """OTTER_DECODE_CACHED_DYN_WORKSPACE_BYTES of include/otter_hip.h."""
-    return N * H * ((S_max + 127) // 128) * 130 * 4
 
 
 def decode_attn_cached_dyn(q, k_new, v_new, k_cache, v_cache, pos_dev, scale, cos_table=None, sin_table=None, src=None, key_valid=None, slopes=None,
@@ -713,81 +783,10 @@ def decode_attn_cached_dyn(q, k_new, v_new, k_cache, v_cache, pos_dev, scale, co
     captured in a graph, serves every step.  Everything else as decode_attn_cached.  Returns o [N,H*128] bf16 (`out`: a contiguous bf16
     [N,H*128] tensor to write instead)."""
     K.require_cuda(q, k_new, v_new, k_cache, v_cache, pos_dev, cos_table, sin_table, src, key_valid, slopes, out)
-    if q.dim() != 3:
-        raise K.OtterHipError("decode_attn_cached_dyn: q must be [N,H,128]")
-    N, H = q.shape[:2]
-    if not (_decode_new_ok(q, N, H) and _decode_new_ok(k_new, N, H) and _decode_new_ok(v_new, N, H)):
-        raise K.OtterHipError("decode_attn_cached_dyn: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
-    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
-    for t in (k_cache, v_cache):
-        if (t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 128) or t.stride(3) != 1 or t.stride(2) != 128
-                or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < S_max * 128 or t.data_ptr() % 16):
-            raise K.OtterHipError("decode_attn_cached_dyn: k_cache / v_cache must be bf16 [N,H,S_max,128] with key stride 128, unit dim stride, 16-B aligned")
-    if S_max < 2 or S_max > DECODE_CACHED_MAX_KEYS:
-        raise K.OtterHipError(f"decode_attn_cached_dyn: S_max={S_max} outside [2, {DECODE_CACHED_MAX_KEYS}]")
-    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
-        raise K.OtterHipError("decode_attn_cached_dyn: pos_dev must be an int32 tensor of one element")
-    if (cos_table is None) != (sin_table is None):
-        raise K.OtterHipError("decode_attn_cached_dyn: cos_table and sin_table must both be given or both be None")
-    tab_stride = 0
-    if cos_table is not None:
-        for t in (cos_table, sin_table):
-            if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != 128 or t.stride(1) != 1 or t.stride(0) < 128
-                    or t.stride() != cos_table.stride()):
-                raise K.OtterHipError("decode_attn_cached_dyn: cos_table / sin_table must be fp32 [>= S_max, 128] with a unit dim stride and equal strides")
-        tab_stride = cos_table.stride(0)
-    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < S_max - 1 or src.stride(1) != 1
-                            or (N > 1 and src.stride(0) < S_max - 1)):
-        raise K.OtterHipError("decode_attn_cached_dyn: src must be int32 [N, >= S_max - 1] with a unit column stride")
-    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < S_max
-                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < S_max)):
-        raise K.OtterHipError("decode_attn_cached_dyn: key_valid must be uint8 [N, >= S_max] with a unit column stride")
-    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
-        raise K.OtterHipError("decode_attn_cached_dyn: slopes must be contiguous fp32 [H]")
-    if out is None:
-        o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
-    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * 128) or not out.is_contiguous():
-        raise K.OtterHipError("decode_attn_cached_dyn: out must be a contiguous bf16 [N, H*128] tensor")
-    else:
-        o = out
-    ws = _ws.get(decode_attn_cached_dyn_workspace_bytes(N, H, S_max), q.device)
-    K.check(K.lib().otter_decode_attn_cached_dyn(
-        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
-        v_new.stride(1), K.ptr(cos_table), K.ptr(sin_table), tab_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1),
-        v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), K.ptr(src), max(src.stride(0), S_max - 1) if src is not None else 0,
-        K.ptr(key_valid), max(key_valid.stride(0), S_max) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(),
-        N, H, pos_dev.data_ptr(), S_max, 128, float(scale), K.stream()), "decode_attn_cached_dyn")
+    args, o = _decode_cached_args("decode_attn_cached_dyn", True, q, k_new, v_new, k_cache, v_cache, None, pos_dev, scale, cos_table, sin_table,
+                                  src, key_valid, slopes, out)
+    K.check(K.lib().otter_decode_attn_cached_dyn(*args, K.stream()), "decode_attn_cached_dyn")
     return o
-
-
-def decode_attn_cached_i8_workspace_bytes(N: int, H: int, Sk: int) -> int:
-    """OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES of include/otter_hip.h."""
-    return N * H * ((Sk + 127) // 128) * 130 * 4
-
-
-def decode_attn_cached_i8_dyn_workspace_bytes(N: int, H: int, S_max: int) -> int:
-    """OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES of include/otter_hip.h."""
-    return N * H * ((S_max + 127) // 128) * 130 * 4
-
-
-def _decode_i8_common(name, q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, slopes):
-    """The checks both int8-cache entry points share; returns (N, H, S_max)."""
-    if q.dim() != 3:
-        raise K.OtterHipError(f"{name}: q must be [N,H,128]")
-    N, H = q.shape[:2]
-    if not (_decode_new_ok(q, N, H) and _decode_new_ok(k_new, N, H) and _decode_new_ok(v_new, N, H)):
-        raise K.OtterHipError(f"{name}: q / k_new / v_new must be bf16 [N,H,128], unit dim stride, strides % 8 == 0, 16-B aligned")
-    S_max = k_cache.shape[2] if k_cache.dim() == 4 else -1
-    for t in (k_cache, v_cache):
-        if (t.dtype != torch.int8 or t.dim() != 4 or tuple(t.shape) != (N, H, S_max, 128) or t.stride(3) != 1 or t.stride(2) != 128
-                or t.stride(0) % 16 or t.stride(1) % 16 or t.stride(1) < S_max * 128 or t.data_ptr() % 16):
-            raise K.OtterHipError(f"{name}: k_cache / v_cache must be int8 [N,H,S_max,128] with key stride 128, unit dim stride, 16-B aligned")
-    for t in (k_scale, v_scale):
-        if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape) != (N, H, S_max) or t.stride(2) != 1 or t.stride(1) < S_max:
-            raise K.OtterHipError(f"{name}: k_scale / v_scale must be fp32 [N,H,S_max] with a unit key stride")
-    if slopes is not None and (slopes.dtype != torch.float32 or not slopes.is_contiguous() or slopes.numel() != H):
-        raise K.OtterHipError(f"{name}: slopes must be contiguous fp32 [H]")
-    return N, H, S_max
 
 
 def decode_attn_cached_i8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos, scale, cos=None, sin=None, src=None, key_valid=None,
@@ -797,33 +796,9 @@ def decode_attn_cached_i8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, p
     with the quantised new token, which is attended in its dequantised form.  Everything else as decode_attn_cached.
     Returns o [N,H*128] bf16."""
     K.require_cuda(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cos, sin, src, key_valid, slopes)
-    N, H, S_max = _decode_i8_common("decode_attn_cached_i8", q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, slopes)
-    pos = int(pos)
-    if S_max > DECODE_CACHED_MAX_KEYS or pos < 1 or pos >= S_max:
-        raise K.OtterHipError(f"decode_attn_cached_i8: pos={pos} outside [1, S_max) with S_max={S_max} (limit {DECODE_CACHED_MAX_KEYS})")
-    if (cos is None) != (sin is None):
-        raise K.OtterHipError("decode_attn_cached_i8: cos and sin must both be given or both be None")
-    cs_stride = 0
-    if cos is not None:
-        for t in (cos, sin):
-            if (t.dtype != torch.float32 or t.shape[-1] != 128 or t.stride(-1) != 1 or tuple(t.shape) not in ((128,), (N, 128))
-                    or tuple(t.shape) != tuple(cos.shape) or t.stride() != cos.stride()):
-                raise K.OtterHipError("decode_attn_cached_i8: cos / sin must be fp32 [128] or [N,128] with a unit dim stride and equal strides")
-        cs_stride = cos.stride(0) if cos.dim() == 2 else 0
-    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < pos or src.stride(1) != 1):
-        raise K.OtterHipError("decode_attn_cached_i8: src must be int32 [N, >= pos] with a unit column stride")
-    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < pos + 1
-                                  or key_valid.stride(1) != 1):
-        raise K.OtterHipError("decode_attn_cached_i8: key_valid must be uint8 [N, >= pos+1] with a unit column stride")
-    o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
-    ws = _ws.get(decode_attn_cached_i8_workspace_bytes(N, H, pos + 1), q.device)
-    K.check(K.lib().otter_decode_attn_cached_i8(
-        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
-        v_new.stride(1), K.ptr(cos), K.ptr(sin), cs_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), v_cache.data_ptr(),
-        v_cache.stride(0), v_cache.stride(1), k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1), v_scale.data_ptr(), v_scale.stride(0),
-        v_scale.stride(1), K.ptr(src), src.stride(0) if src is not None else 0, K.ptr(key_valid),
-        key_valid.stride(0) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H, pos, S_max, 128,
-        float(scale), K.stream()), "decode_attn_cached_i8")
+    args, o = _decode_cached_args("decode_attn_cached_i8", False, q, k_new, v_new, k_cache, v_cache, (k_scale, v_scale), pos, scale, cos, sin,
+                                  src, key_valid, slopes, None)
+    K.check(K.lib().otter_decode_attn_cached_i8(*args, K.stream()), "decode_attn_cached_i8")
     return o
 
 
@@ -832,40 +807,9 @@ def decode_attn_cached_i8_dyn(q, k_new, v_new, k_cache, v_cache, k_scale, v_scal
     """decode_attn_cached_dyn over an int8 cache (otter_decode_attn_cached_i8_dyn): the caches and scales of decode_attn_cached_i8, every
     other argument as decode_attn_cached_dyn.  Returns o [N,H*128] bf16 (`out`: a contiguous bf16 [N,H*128] tensor to write instead)."""
     K.require_cuda(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos_dev, cos_table, sin_table, src, key_valid, slopes, out)
-    N, H, S_max = _decode_i8_common("decode_attn_cached_i8_dyn", q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, slopes)
-    if S_max < 2 or S_max > DECODE_CACHED_MAX_KEYS:
-        raise K.OtterHipError(f"decode_attn_cached_i8_dyn: S_max={S_max} outside [2, {DECODE_CACHED_MAX_KEYS}]")
-    if pos_dev.dtype != torch.int32 or pos_dev.numel() != 1:
-        raise K.OtterHipError("decode_attn_cached_i8_dyn: pos_dev must be an int32 tensor of one element")
-    if (cos_table is None) != (sin_table is None):
-        raise K.OtterHipError("decode_attn_cached_i8_dyn: cos_table and sin_table must both be given or both be None")
-    tab_stride = 0
-    if cos_table is not None:
-        for t in (cos_table, sin_table):
-            if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < S_max or t.shape[1] != 128 or t.stride(1) != 1 or t.stride(0) < 128
-                    or t.stride() != cos_table.stride()):
-                raise K.OtterHipError("decode_attn_cached_i8_dyn: cos_table / sin_table must be fp32 [>= S_max, 128] with a unit dim stride and equal strides")
-        tab_stride = cos_table.stride(0)
-    if src is not None and (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != N or src.shape[1] < S_max - 1 or src.stride(1) != 1
-                            or (N > 1 and src.stride(0) < S_max - 1)):
-        raise K.OtterHipError("decode_attn_cached_i8_dyn: src must be int32 [N, >= S_max - 1] with a unit column stride")
-    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.dim() != 2 or key_valid.shape[0] != N or key_valid.shape[1] < S_max
-                                  or key_valid.stride(1) != 1 or (N > 1 and key_valid.stride(0) < S_max)):
-        raise K.OtterHipError("decode_attn_cached_i8_dyn: key_valid must be uint8 [N, >= S_max] with a unit column stride")
-    if out is None:
-        o = torch.empty((N, H * 128), dtype=torch.bfloat16, device=q.device)
-    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H * 128) or not out.is_contiguous():
-        raise K.OtterHipError("decode_attn_cached_i8_dyn: out must be a contiguous bf16 [N, H*128] tensor")
-    else:
-        o = out
-    ws = _ws.get(decode_attn_cached_i8_dyn_workspace_bytes(N, H, S_max), q.device)
-    K.check(K.lib().otter_decode_attn_cached_i8_dyn(
-        q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
-        v_new.stride(1), K.ptr(cos_table), K.ptr(sin_table), tab_stride, k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1),
-        v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1), v_scale.data_ptr(),
-        v_scale.stride(0), v_scale.stride(1), K.ptr(src), max(src.stride(0), S_max - 1) if src is not None else 0, K.ptr(key_valid),
-        max(key_valid.stride(0), S_max) if key_valid is not None else 0, K.ptr(slopes), o.data_ptr(), ws.data_ptr(), ws.numel(), N, H,
-        pos_dev.data_ptr(), S_max, 128, float(scale), K.stream()), "decode_attn_cached_i8_dyn")
+    args, o = _decode_cached_args("decode_attn_cached_i8_dyn", True, q, k_new, v_new, k_cache, v_cache, (k_scale, v_scale), pos_dev, scale,
+                                  cos_table, sin_table, src, key_valid, slopes, out)
+    K.check(K.lib().otter_decode_attn_cached_i8_dyn(*args, K.stream()), "decode_attn_cached_i8_dyn")
     return o
 
 
