@@ -252,9 +252,11 @@ int otter_attn_bwd(const void* q, int64_t q_stride, const void* k, const void* v
  * the kernel.  q/k/v/o (and the gradients) are [B, S, H, 128] views given by element strides, so the three slices
  * of a fused Wqkv output and of its gradient buffer are addressed in place (no chunk/cat copies).
  * lse [B,H,Sq] fp32 (natural log) is written by the forward and read by the backward; delta is backward workspace of
- * 2*B*H*Sq floats (row dot products, then a log2-domain copy of lse).  A query row with no visible key yields 0 (lse = -inf) and zero gradients; the reference's
- * masked_fill(finfo.min) would yield the uniform average there -- such rows only exist for left-padded prompts,
- * which the host routes to its SDPA path.
+ * 2*B*H*Sq floats (row dot products, then a log2-domain copy of lse).  A query row with no visible key yields o = 0, lse = -inf and zero gradients (exactly: tests/test_gpu_flash_exact.py); the
+ * reference's masked_fill(finfo.min) would yield the uniform average there.  Such rows exist for left-padded prompts (the padded
+ * positions themselves) and for Sq > Sk under the causal mask (rows i < Sq - Sk); nobody consumes them.  Inference passes over
+ * left-padded prompts take this kernel (mpt.py, llama.py, fuyu.py); only a left-padded batch that needs gradients goes to the
+ * host's SDPA path.  Sq != Sk is supported by every kernel, forward and backward.
  * head_dim 64: one workgroup takes two adjacent heads (H must be even); the second head of a pair lies head_stride elements after
  * the first inside the same token row (64 <= head_stride <= seq_stride - 64), so compact [B,S,H,64] tensors and the v slots of
  * Persimmon's per-head interleaved [B,S,H,3,64] projection buffer (head_stride 192) are both read / written in place.
