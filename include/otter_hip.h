@@ -614,6 +614,42 @@ int otter_beam_step(const float* logp, int64_t logp_stride, float* beam_scores, 
                     int32_t* hyp_count, double* hyp_worst, int32_t* all_done, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_select_step -- the token selection of generate() (otter_amd/generation.py: generate_tokens, num_beams == 1) in ONE launch per
+ * step: the step's token of every row from the processed scores, written into the preallocated history, with the host loop's
+ * unfinished / eos bookkeeping.  One workgroup per row; no allocation, no synchronise, no sort; the scores are never written.
+ *   scores   fp32 [N, V], row stride (elements, >= V), 4-byte aligned.  1 <= V <= OTTER_SELECT_STEP_MAX_VOCAB.  Read only.
+ *   ids_buf  int64 [N, max_len], row stride (>= max_len), 8-byte aligned; ONLY column L is written.  0 <= L < max_len <= 2^30.
+ *   mode     OTTER_SELECT_GREEDY or OTTER_SELECT_SAMPLE.  inv_temperature, top_k, top_p, q are read in sample mode only.
+ * GREEDY: the index of the row maximum.  TIE RULE: among equal maxima the first index wins (-0 equals +0); a NaN counts as the maximum
+ * and the first NaN wins -- torch.argmax's rule.
+ * SAMPLE: inv_temperature fp32 (finite, > 0: the host's fp32 1 / T), top_k >= 0 (0 = off), top_p in (0, 1] (1 = off), q fp32 [N, V]
+ * with row stride q_stride (>= V): the exponential draws, `torch.empty_like(p).exponential_(1)` -- torch.multinomial(p, 1) is
+ * argmax(p / q) over exactly these draws.  Per row:
+ *   s'_j = fp32(s_j * inv_temperature), rounded before anything else uses it (never contracted into the subtraction below); m = max s'.
+ *   top-k: k = min(max(top_k, 1), V), v_k = the k-th largest s'; keep s'_j >= v_k.  ALL ties at v_k stay: the host's `scores < kth`
+ *       rule, so the kept set is the host's bit for bit.
+ *   top-p, over the top-k survivors: w_j = floor(expf(s'_j - m) * 2^40) (a 64-bit integer; expf in fp32), Z = sum w_j,
+ *       R = min(floor((1 - top_p) * (double)Z), Z - 1) with 1 - top_p in fp64; a value v is kept iff  sum of w_j over s'_j <= v  >  R.
+ *       The maximum is always kept.  This is the host rule (ascending, `cumsum(softmax) <= 1 - top_p` is removed) with the mass in
+ *       integers, so that no summation order can move the threshold, and with ONE DIFFERENCE: equal values are kept or removed
+ *       TOGETHER, where the host's unstable sort splits a tie group that straddles the boundary arbitrarily.  Apart from rounding at
+ *       the boundary this is the only place where the kept set can differ from the host's.
+ *   draw: the kept j that maximises expf(s'_j - m) / q_j, an IEEE fp32 division (q_j = 0 gives inf, as on the host; a NaN ratio never
+ *       wins).  TIE RULE: the smaller j among equal ratios.
+ *   A row with a NaN score, or whose maximum s' is not finite, returns SOME token in [0, V) (the host path raises there).
+ * Bookkeeping, both modes, with `sel` the selected token: ids_buf[r, L] = unfinished[r] ? sel : pad_token_id; if unfinished[r] and sel
+ * is in eos (int32 [n_eos], NULL when n_eos == 0), unfinished[r] becomes 0 and *n_unfinished (int32) is decremented by an integer
+ * atomic.  unfinished is uint8 [N] (1 = still generating; only ever cleared), n_unfinished starts at the number of ones in it.
+ * Deterministic: every histogram is integer, so the same inputs give the same tokens on every call.
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_SELECT_STEP_MAX_VOCAB 262144
+#define OTTER_SELECT_GREEDY 0
+#define OTTER_SELECT_SAMPLE 1
+int otter_select_step(const float* scores, int64_t scores_stride, int64_t N, int64_t V, int64_t* ids_buf, int64_t ids_stride, int64_t L,
+                      int64_t max_len, int mode, float inv_temperature, int64_t top_k, double top_p, const float* q, int64_t q_stride,
+                      uint8_t* unfinished, int32_t* n_unfinished, const int32_t* eos, int64_t n_eos, int64_t pad_token_id, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * OtterHD / Fuyu-8B path (config C5): row-wise kernels of the Persimmon decoder and the patch scatter.
  *   otter_qk_norm_rope_fwd  /root/reference/src/otter_ai/models/fuyu/modeling_persimmon.py:262-304: the per-head interleaved
  *       projection output qkv [tokens, H, 3, 64] (bf16) is read in place; q and k get LayerNorm over the 64-wide head

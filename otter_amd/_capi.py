@@ -156,6 +156,8 @@ SIGNATURES = {
     "otter_beam_step_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "otter_beam_step": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "otter_select_step": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _f32, _i64, C.c_double, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+                                 _vp]),
     "otter_qk_norm_rope_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _i64, _vp]),
     "otter_qk_norm_rope_bwd_blocks": (_i64, [_i64, _i64]),
     "otter_qk_norm_rope_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),

@@ -16,7 +16,10 @@ re-forward).  Pinned by tests/test_generation.py against `transformers`' own gen
 On device tensors the tensor-valued logits processors are one HIP launch per step (`ops.logits_process`, csrc/logits.hip; OTTER_HIP_LOGITS=0
 switches back); the host loop below is the only path for CPU tensors and the reference that kernel is tested against, bit for bit.  Plain beam
 search on device tensors likewise runs candidate selection, the scorer and the reorder in `ops.beam_step` (csrc/beam.hip, `_DeviceBeam`;
-OTTER_HIP_BEAM=0 switches back to the host block, which stays the path of CPU tensors, beam-sample and group beam search).
+OTTER_HIP_BEAM=0 switches back to the host block, which stays the path of CPU tensors, beam-sample and group beam search).  With
+`num_beams == 1` the step's token is chosen on the device too (`ops.select_step`, csrc/select.hip, `_DeviceSelect`): greedy by default
+(OTTER_HIP_SELECT=0 switches back to the host block), temperature / top-k / top-p sampling when the caller asks for it with
+`device_sampling=True` -- its rule is stated in include/otter_hip.h and restated in torch by `_select_reference`, the path of CPU tensors.
 """
 from __future__ import annotations
 
@@ -301,6 +304,106 @@ class _DeviceBeam:
         return hyps, [bool(d) for d in h["done"].tolist()], h["beam_scores"]
 
 
+# ---- token selection on the device (csrc/select.hip) --------------------------------------------------------------------------------------
+
+
+def inv_temperature_f32(temperature) -> Optional[float]:
+    """fp32(1) / fp32(temperature) as a Python float, what ops.select_step multiplies the scores by; None when the temperature or its
+    reciprocal is not a finite positive fp32 number (the host block then keeps the call)."""
+    try:
+        t = torch.tensor(1.0 if temperature is None else float(temperature), dtype=torch.float32)
+    except (TypeError, ValueError, OverflowError):
+        return None
+    inv = float(torch.ones((), dtype=torch.float32) / t)
+    return inv if (math.isfinite(float(t)) and float(t) > 0.0 and math.isfinite(inv) and inv > 0.0) else None
+
+
+def _select_reference(scores: torch.Tensor, q: torch.Tensor, inv_t: float, top_k: int, top_p: float) -> torch.Tensor:
+    """The sample rule of otter_select_step (include/otter_hip.h) restated in torch, in the same fp32 arithmetic and with the same tie rules:
+    the token [N] int64 of every row of scores fp32 [N, V] under the exponential draws q [N, V].  The path of `device_sampling=True` on CPU
+    tensors and with OTTER_HIP_SELECT=0, and what the kernel is compared with."""
+    s = scores.float() * float(inv_t) + 0.0                      # s' (the sum turns -0 into +0; values compare equal either way)
+    q = q.float()
+    N, V = s.shape
+    out = torch.empty(N, dtype=torch.long, device=s.device)
+    for r in range(N):
+        row = s[r]
+        m = row.max()
+        if not bool(torch.isfinite(m)):                          # a NaN or no finite score: some token (the arg max; the host path raises here)
+            out[r] = torch.argmax(row)
+            continue
+        keep = torch.ones(V, dtype=torch.bool, device=s.device)
+        if top_k and top_k > 0:
+            kth = torch.topk(row, min(max(int(top_k), 1), V))[0][-1]
+            keep = row >= kth
+        e = torch.exp(row - m)
+        if top_p < 1.0:
+            vals, order = torch.sort(row[keep])
+            w = (e[keep][order].double() * float(2 ** 40)).to(torch.int64)     # floor: the numerators are >= 0
+            cum = w.cumsum(0)                                    # exact: at most 2^18 terms of at most 2^40
+            Z = int(cum[-1])
+            R = min(int((1.0 - float(top_p)) * float(Z)), Z - 1)
+            group_cum = cum[torch.searchsorted(vals, vals, right=True) - 1]      # equal values are kept or removed together
+            keep = keep & (row >= vals[group_cum > R][0])
+        ratio = e / q[r]
+        ratio = torch.where(keep & ~torch.isnan(ratio), ratio, torch.full_like(ratio, -1.0))
+        out[r] = (ratio == ratio.max()).nonzero()[0, 0]          # the smaller index among equal ratios
+    return out
+
+
+class _DeviceSelect:
+    """The state of one greedy or sampled generation on the device, allocated once per generate_tokens call at fixed addresses: the token
+    history [B, max_len] and the attention mask [B, max_len] (the step is handed [:, :L] views: nothing is concatenated), `unfinished`, the
+    4-byte count of unfinished rows, the eos list and, in sample mode, the buffer of exponential draws.  `step` is one ops.select_step call
+    (and, in sample mode, the refill of the draws)."""
+
+    @staticmethod
+    def usable(scores: torch.Tensor, ids: torch.Tensor, mask: Optional[torch.Tensor]) -> bool:
+        return (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1 and ids.device == scores.device
+                and ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == scores.shape[0] and scores.shape[0] >= 1
+                and 1 <= scores.shape[1] <= ops.SELECT_STEP_MAX_VOCAB and (mask is None or mask.device == scores.device)
+                and os.environ.get("OTTER_HIP_SELECT", "1") != "0")
+
+    def __init__(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], max_len: int, eos_t: Optional[torch.Tensor],
+                 pad_token_id: int, sample: Optional[Tuple[float, int, float]], generator: Optional[torch.Generator]):
+        B, L0 = input_ids.shape
+        dev = input_ids.device
+        self.L, self.max_len, self.pad, self.sample, self.generator = L0, max_len, int(pad_token_id), sample, generator
+        self.ids_buf = torch.zeros(B, max_len, dtype=torch.int64, device=dev)
+        self.ids_buf[:, :L0] = input_ids
+        self.mask_buf = None
+        if attention_mask is not None:
+            self.mask_buf = torch.ones(B, max_len, dtype=attention_mask.dtype, device=dev)
+            self.mask_buf[:, :L0] = attention_mask
+        self.unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        self.n_unfinished = torch.full((1,), B, dtype=torch.int32, device=dev)
+        self.eos_t = eos_t.to(torch.int32) if eos_t is not None else None          # (the loop's device list: no further copy from the host)
+        self.q = None
+
+    def views(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        return self.ids_buf[:, :self.L], (self.mask_buf[:, :self.L] if self.mask_buf is not None else None)
+
+    def step(self, scores: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Writes the step's tokens into column L; (ids [B, L + 1], mask [B, L + 1] or None), views of the buffers."""
+        if self.sample is None:
+            ops.select_step(scores, self.ids_buf, self.L, self.unfinished, self.n_unfinished, self.eos_t, self.pad)
+        else:
+            if self.q is None:
+                self.q = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)
+            self.q.exponential_(1, generator=self.generator)     # the draws torch.multinomial makes: a seeded generator advances as before
+            inv_t, k, p = self.sample
+            ops.select_step(scores, self.ids_buf, self.L, self.unfinished, self.n_unfinished, self.eos_t, self.pad, True, inv_t, k, p, self.q)
+        self.L += 1
+        return self.views()
+
+    def all_finished(self) -> bool:
+        """The 4-byte count: the one synchronising read of a step (made only when an eos list exists -- nothing finishes early without one)."""
+        return int(self.n_unfinished.item()) <= 0
+
+    def result(self) -> torch.Tensor:
+        return self.ids_buf[:, :self.L].contiguous()
+
+
 # ---- the loop ----------------------------------------------------------------------------------------------------------
 
 # step(ids [N,L], mask [N,L] or None, past, beam_idx [N] or None) -> (last-position logits [N,V], past)
@@ -323,7 +426,7 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
                     bad_words_ids=None, min_new_tokens: int = 0, min_length: int = 0, repetition_penalty: float = 1.0,
                     do_sample: bool = False, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                     generator: Optional[torch.Generator] = None, num_beam_groups: int = 1, diversity_penalty: float = 0.0,
-                    prefix_allowed_tokens_fn=None, _identical_groups_ok: bool = False, **unused) -> torch.Tensor:
+                    prefix_allowed_tokens_fn=None, device_sampling: bool = False, _identical_groups_ok: bool = False, **unused) -> torch.Tensor:
     """Returns input_ids with the generated tokens appended ([B * num_return_sequences, L + new], right-padded with
     pad_token_id after eos), exactly the tensor `GenerationMixin.generate` returns for a decoder-only model."""
     if unused:
@@ -332,6 +435,8 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
             raise NotImplementedError("otter_amd.generate: unsupported generation arguments %s" % bad)
     if num_return_sequences != 1 and not (num_beams > 1 and num_return_sequences <= num_beams):
         raise NotImplementedError("num_return_sequences > 1 needs num_beams >= num_return_sequences (beam search)")
+    if device_sampling and (num_beams != 1 or not do_sample):
+        raise ValueError("`device_sampling` chooses how `do_sample=True` with `num_beams == 1` draws its token: it needs both")
     num_beam_groups = int(num_beam_groups or 1)
     diversity_penalty = float(diversity_penalty or 0.0)
     if num_beam_groups > 1:    # GenerationConfig.validate's rules for the group mode
@@ -358,10 +463,31 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
     if num_beams == 1:
         ids, mask, past = input_ids, attention_mask, None
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        rule = None                    # device_sampling: (fp32 1 / T, top_k, top_p) of the stated rule; None: the host block below draws
+        if device_sampling:
+            inv_t, p = inv_temperature_f32(temperature), float(top_p if top_p is not None else 1.0)
+            if inv_t is not None and 0.0 < p <= 1.0:
+                rule = (inv_t, max(int(top_k or 0), 0), p)
+        dsel, first = None, True       # the device path's state (_DeviceSelect), decided at the first step from the tensors it would read
         while ids.shape[1] < max_len:
             logits, past = step(ids, mask, past, None)
             scores = proc(ids, logits.float().clone())
-            if do_sample:
+            if first:
+                first = False
+                if ((not do_sample or rule is not None) and all(-2 ** 31 <= e < 2 ** 31 for e in eos)
+                        and _DeviceSelect.usable(scores, ids, mask)):
+                    dsel = _DeviceSelect(ids, mask, max_len, eos_t, pad_token_id, rule, generator)
+            if dsel is not None:
+                # the token, the pad of finished rows, the append and the eos bookkeeping in one ops.select_step call (csrc/select.hip); ids and
+                # mask become [:, :L + 1] views of buffers allocated once.  Without an eos list nothing here synchronises.
+                ids, mask = dsel.step(scores)
+                if eos and dsel.all_finished():
+                    break
+                continue
+            if rule is not None:       # CPU tensors or OTTER_HIP_SELECT=0: the kernel's rule restated in torch, over the same draws
+                q = torch.empty(scores.shape, dtype=torch.float32, device=scores.device).exponential_(1, generator=generator)
+                nxt = _select_reference(scores, q, *rule)
+            elif do_sample:
                 if temperature is not None and temperature != 1.0:
                     scores = scores / float(temperature)
                 scores = _top_k_top_p(scores, int(top_k or 0), float(top_p if top_p is not None else 1.0))
@@ -376,7 +502,7 @@ def generate_tokens(step: StepFn, input_ids: torch.Tensor, attention_mask: Optio
                 unfinished = unfinished & ~torch.isin(nxt, eos_t)
                 if not bool(unfinished.any()):
                     break
-        return ids
+        return ids if dsel is None else dsel.result()
 
     if num_beam_groups > 1:
         return _group_beam_search(step, input_ids, attention_mask, proc, eos, pad_token_id, max_len, int(num_beams), num_beam_groups,

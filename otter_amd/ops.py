@@ -947,12 +947,12 @@ def dequant_w8(qweight, scale, out=None):
 LOGITS_PROCESS_MAX_VOCAB = 262144     # include/otter_hip.h: the V-bit ownership bitmap of otter_logits_process
 
 
-def _i32_list(name, t, device):
-    """(pointer, length) of an optional contiguous int32 1-d list on `device`."""
+def _i32_list(name, t, device, op="logits_process"):
+    """(pointer, length) of an optional contiguous int32 1-d list on `device`; `op` names the operator in the error."""
     if t is None or t.numel() == 0:
         return None, 0
     if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
-        raise K.OtterHipError(f"logits_process: {name} must be a contiguous int32 1-d tensor on the scores' device")
+        raise K.OtterHipError(f"{op}: {name} must be a contiguous int32 1-d tensor on the scores' device")
     return t.data_ptr(), t.numel()
 
 
@@ -1038,6 +1038,43 @@ def beam_step(logp, beam_scores, ids, ids_next, beam_idx, eos, pad_token_id, nb,
                                     all_done.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), K.stream()),
             "beam_step")
     return ids_next, beam_idx
+
+
+SELECT_STEP_MAX_VOCAB = 262144        # include/otter_hip.h: OTTER_SELECT_STEP_MAX_VOCAB, the cap otter_logits_process has
+
+
+def select_step(scores, ids_buf, L, unfinished, n_unfinished, eos=None, pad_token_id=0, sample=False, inv_temperature=1.0, top_k=0, top_p=1.0,
+                q=None):
+    """The step's token of every row in one launch (otter_select_step, csrc/select.hip; include/otter_hip.h states the rule and the tie
+    rules): from scores fp32 [N, V] (unit column stride, V <= SELECT_STEP_MAX_VOCAB, never written) the row maximum, or with `sample` the
+    draw under inv_temperature / top_k (0 = off) / top_p (1 = off) against the exponential draws q fp32 [N, V], written into column L of
+    ids_buf int64 [N, max_len]; unfinished (bool or uint8 [N]) and n_unfinished (int32 [1]) are updated from the int32 `eos` list tensor (or
+    None).  Nothing here synchronises or allocates.  Returns ids_buf."""
+    K.require_cuda(scores, ids_buf, unfinished, n_unfinished, eos, q)
+    if scores.dim() != 2 or ids_buf.dim() != 2 or scores.shape[0] != ids_buf.shape[0] or scores.device != ids_buf.device:
+        raise K.OtterHipError("select_step: scores [N, V] and ids_buf [N, max_len] of equal N on one device")
+    if scores.dtype != torch.float32 or ids_buf.dtype != torch.int64 or scores.stride(1) != 1 or ids_buf.stride(1) != 1:
+        raise K.OtterHipError("select_step: scores fp32 and ids_buf int64, both with a unit column stride")
+    N, V = scores.shape
+    max_len, L = ids_buf.shape[1], int(L)
+    if N < 1 or not 1 <= V <= SELECT_STEP_MAX_VOCAB or not 0 <= L < max_len:
+        raise K.OtterHipError(f"select_step: N={N} must be >= 1, V={V} within 1..{SELECT_STEP_MAX_VOCAB} and L={L} within 0..max_len-1={max_len - 1}")
+    dev = scores.device
+    if (unfinished.dtype not in (torch.bool, torch.uint8) or unfinished.numel() != N or not unfinished.is_contiguous() or unfinished.device != dev
+            or n_unfinished.dtype != torch.int32 or n_unfinished.numel() != 1 or n_unfinished.device != dev):
+        raise K.OtterHipError("select_step: unfinished must be a contiguous bool / uint8 [N] and n_unfinished an int32 [1], on the scores' device")
+    q_p, q_rs = None, 0
+    if sample:
+        if q is None or q.dtype != torch.float32 or tuple(q.shape) != (N, V) or q.stride(1) != 1 or q.device != dev:
+            raise K.OtterHipError("select_step: sample mode needs q, fp32 [N, V] with a unit column stride on the scores' device")
+        q_p, q_rs = q.data_ptr(), (q.stride(0) if N > 1 else max(q.stride(0), V))
+    eos_p, n_eos = _i32_list("eos", eos, dev, "select_step")
+    s_rs = scores.stride(0) if N > 1 else max(scores.stride(0), V)      # (the row stride of a one-row view is arbitrary)
+    i_rs = ids_buf.stride(0) if N > 1 else max(ids_buf.stride(0), max_len)
+    K.check(K.lib().otter_select_step(scores.data_ptr(), s_rs, N, V, ids_buf.data_ptr(), i_rs, L, max_len, 1 if sample else 0,
+                                      float(inv_temperature), int(top_k), float(top_p), q_p, q_rs, unfinished.data_ptr(),
+                                      n_unfinished.data_ptr(), eos_p, n_eos, int(pad_token_id), K.stream()), "select_step")
+    return ids_buf
 
 
 def qk_norm_rope_fwd(qkv, gq, bq, gk, bk, cos, sin, H, rot, eps, width=128, copy_v=True):

@@ -22,7 +22,17 @@ the scorer and the reorder -- in `ops.beam_step` (csrc/beam.hip) against the hos
 loop, three copies back), with the logits processors on the kernel on both paths; the beam points only (the greedy point has no such block).
 `--b8` / `--no-b8` keeps or drops the B = 8 points (the longest ones).
 
-  python tools/generate_e2e_bench.py [--switch logits|beam] [--points mpt fuyu] [--rounds 3] [--new 128] [--out profiles/r16_logits_process_ab.txt]"""
+`--switch select` and `--switch sample` measure the token selection of `num_beams == 1` in `ops.select_step`
+(csrc/select.hip) at greedy / sampled points of their own -- mpt-tuple-B1 and mpt-graph-B1 / -B4 / -B8 without beams, fuyu-graph with one
+row -- with the logits processors on the kernel on both paths.  `select` alternates OTTER_HIP_SELECT on greedy calls (argmax, where, two cats,
+isin and the synchronising any() against one launch).  `sample` alternates the host sampler against `device_sampling=True` at
+`top_k=50, top_p=0.9, temperature=0.7` under one seed: the two follow different tie and rounding rules (include/otter_hip.h), so where their
+tokens differ one more call runs the torch restatement of the kernel's rule (`device_sampling=True`, OTTER_HIP_SELECT=0) over the same draws
+and the tool reports whether THAT equals the kernel path -- if so the kernel follows its stated rule -- and one more host-sampler call counts
+the steps at which the host splits a group of equal values at the top-p boundary, beside the first position at which the tokens differ.
+Several switches may be given: the models are built once.
+
+  python tools/generate_e2e_bench.py [--switch logits|beam|select|sample ...] [--points mpt fuyu] [--rounds 3] [--new 128] [--out FILE]"""
 from __future__ import annotations
 
 import argparse
@@ -40,8 +50,10 @@ import torch  # noqa: E402
 
 PATHS = ("host", "kernel")
 SWITCH = {"host": "0", "kernel": "1"}
-SWITCH_VAR = {"logits": "OTTER_HIP_LOGITS", "beam": "OTTER_HIP_BEAM"}
-WHAT = {"logits": "logits processors", "beam": "beam-search block"}
+SWITCH_VAR = {"logits": "OTTER_HIP_LOGITS", "beam": "OTTER_HIP_BEAM", "select": "OTTER_HIP_SELECT", "sample": "OTTER_HIP_SELECT"}
+WHAT = {"logits": "logits processors", "beam": "beam-search block", "select": "greedy token selection", "sample": "token sampling"}
+SYMBOL = {"logits": "otter_logits_process", "beam": "otter_beam_step", "select": "otter_select_step", "sample": "otter_select_step"}
+SAMPLE = dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7)
 switch = "logits"                      # --switch
 THRESHOLD = 1.03
 BAD_WORDS = [[11], [12, 13]]
@@ -53,12 +65,15 @@ FUYU_VOCAB = 262144
 
 @torch.no_grad()
 def timed(call, path):
-    """(seconds, tokens on the host) of one whole generate call on `path`."""
-    os.environ[SWITCH_VAR[switch]] = SWITCH[path]
+    """(seconds, tokens on the host) of one whole generate call on `path` ("restated": --switch sample's diagnosis call)."""
+    os.environ[SWITCH_VAR[switch]] = "1" if switch == "sample" and path != "restated" else SWITCH.get(path, "0")
+    extra = {}
+    if switch == "sample":
+        extra = dict(SAMPLE, device_sampling=path != "host", generator=torch.Generator(device="cuda").manual_seed(1234))
     gc.collect()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    toks = call()
+    toks = call(**extra)
     torch.cuda.synchronize()
     return time.perf_counter() - t0, toks.cpu()
 
@@ -87,6 +102,34 @@ def tie_diagnosis(call, kernel_tokens):
     return first, torch.equal(toks, kernel_tokens)
 
 
+def sample_diagnosis(call, host_tokens, kernel_tokens, new):
+    """--switch sample, after the clock, when the host sampler and the kernel path returned different tokens.  The two follow different rules
+    in two places (include/otter_hip.h): the host's unstable sort splits a group of equal values that straddles the top-p boundary where the
+    kernel keeps or removes the group together, and the host normalises the softmax before the race.  Two more calls: the torch restatement of
+    the kernel's rule over the same draws (does it return the kernel path's tokens?), and the host sampler with `_top_k_top_p` watched: a step
+    SPLITS when, in some row, a value equal to the smallest kept one was removed.  Returns (restatement equals kernel, the first generated
+    position at which host and kernel tokens differ, the host path's steps that split, as a list)."""
+    from otter_amd import generation as G
+
+    by_rule = torch.equal(timed(call, "restated")[1], kernel_tokens)
+    real, split = G._top_k_top_p, []
+
+    def watched(scores, top_k, top_p, min_keep=1):
+        out = real(scores, top_k, top_p, min_keep)
+        kept = out > float("-inf")
+        smallest = torch.where(kept, scores, torch.full_like(scores, float("inf"))).amin(-1, keepdim=True)
+        split.append(((scores == smallest) & ~kept).any())
+        return out
+
+    G._top_k_top_p = watched
+    try:
+        timed(call, "host")
+    finally:
+        G._top_k_top_p = real
+    differ = (host_tokens[:, -new:] != kernel_tokens[:, -new:]).any(0).nonzero().flatten().tolist()
+    return by_rule, (differ[0] if differ else None), [s for s, flag in enumerate(split) if bool(flag)]
+
+
 def measure(tag, call, new, rounds, say):
     """Warm-up, then `rounds` alternating rounds; returns the point's record."""
     first = first_tokens = {p: timed(call, p)[1] for p in PATHS}  # warm-up: allocator, kernel loads, workspaces; and the tokens
@@ -108,6 +151,14 @@ def measure(tag, call, new, rounds, say):
     rec = {"ms_per_position": t, "median": med, "spread": spread, "kernel_over_host": ratio, "tokens_equal": same}
     if not same:
         say("TOKENS DIFFER: %s" % tag)
+        if switch == "sample":
+            by_rule, first_diff, splits = sample_diagnosis(call, first_tokens["host"], first_tokens["kernel"], new)
+            say("%s: the torch restatement of the kernel's rule (device_sampling=True, OTTER_HIP_SELECT=0) over the same draws against the kernel "
+                "path: tokens equal: %s.  Host sampler against kernel path: the tokens first differ at generated position %s; on the host path a "
+                "group of equal values is split at the top-p boundary in %d of %d steps, first at step %s (the kernel keeps or removes such a group "
+                "together; where no split precedes the first difference, rounding and the host's normalisation before the race are what is left)"
+                % (tag, by_rule, first_diff, len(splits), new, splits[0] if splits else None))
+            rec["tokens_equal_restatement"], rec["first_difference"], rec["split_steps"] = by_rule, first_diff, splits
         if switch == "beam":
             first, by_rule = tie_diagnosis(call, first_tokens["kernel"])
             say("%s: the host path's first tie among the top n_cand + 1 sums of a sentence is at step %s (torch.topk promises no order there); "
@@ -127,20 +178,30 @@ def mpt_points(a, say, result):
         vx, ids, _, _, _ = bench.synth_batch(model, B, a.prompt, "cuda:0", seed=17)
         vx = vx.to(torch.bfloat16)
 
-        def call():
+        def call(**extra):
             with torch.autocast("cuda", dtype=torch.bfloat16):
-                return model.generate(vision_x=vx, lang_x=ids, max_new_tokens=a.new, eos_token_id=-1, pad_token_id=0, **kw)
+                return model.generate(vision_x=vx, lang_x=ids, max_new_tokens=a.new, eos_token_id=-1, pad_token_id=0, **kw, **extra)
 
         result[tag] = measure(tag, call, a.new, a.rounds, say)
 
+    global switch
     batches = (8, 1) if a.b8 else (1,)
-    for B in batches:
-        point("mpt-tuple-B%d (bf16, tuple cache, 3 beams)" % B, B, dict(BEAM, use_cache=True))
+    for switch in a.switch:
+        if switch in ("select", "sample"):
+            point("%s: mpt-tuple-B1 (bf16, tuple cache, no beams)" % switch, 1, dict(GREEDY, use_cache=True))
+            continue
+        for B in batches:
+            point("mpt-tuple-B%d (bf16, tuple cache, 3 beams)" % B, B, dict(BEAM, use_cache=True))
     model.quantize_decoder_int8()
-    for B in batches:
-        point("mpt-graph-B%d (int8, static + cross-attention cache, graph replay, 3 beams)" % B, B, dict(BEAM, **FAST))
-    if switch == "logits":
-        point("mpt-greedy-B4 (int8, static + cross-attention cache, graph replay, greedy)", 4, dict(GREEDY, **FAST))
+    for switch in a.switch:
+        if switch in ("select", "sample"):
+            for B in ((1, 4, 8) if a.b8 else (1, 4)):
+                point("%s: mpt-graph-B%d (int8, static + cross-attention cache, graph replay, no beams)" % (switch, B), B, dict(GREEDY, **FAST))
+            continue
+        for B in batches:
+            point("mpt-graph-B%d (int8, static + cross-attention cache, graph replay, 3 beams)" % B, B, dict(BEAM, **FAST))
+        if switch == "logits":
+            point("mpt-greedy-B4 (int8, static + cross-attention cache, graph replay, greedy)", 4, dict(GREEDY, **FAST))
     del model
     gc.collect()
     torch.cuda.empty_cache()
@@ -158,14 +219,25 @@ def fuyu_points(a, say, result):
     say("Persimmon at Fuyu-8B shape, %d layers, vocabulary %d, int8 decoder, random init; prompt %d; %d new tokens"
         % (a.fuyu_layers, FUYU_VOCAB, a.fuyu_prompt, a.new))
     ids = torch.randint(0, FUYU_VOCAB, (1, a.fuyu_prompt), generator=torch.Generator().manual_seed(1)).cuda()
-    cache = StaticKVCache.for_model(model, rows=3, max_len=a.fuyu_prompt + a.new + 1)
+    global switch
+    cache = None
+    for switch in a.switch:
+        kw = dict(GREEDY) if switch in ("select", "sample") else BEAM
+        rows = kw.get("num_beams", 1)
+        if cache is None or cache.rows != rows:
+            cache = None
+            gc.collect()
+            torch.cuda.empty_cache()
+            cache = StaticKVCache.for_model(model, rows=rows, max_len=a.fuyu_prompt + a.new + 1)
 
-    def call():
-        cache.reset()
-        return model.generate(ids, max_new_tokens=a.new, eos_token_id=-1, pad_token_id=0, past_key_values=cache, graph_decode=True, **BEAM)
+        def call(**extra):
+            cache.reset()
+            return model.generate(ids, max_new_tokens=a.new, eos_token_id=-1, pad_token_id=0, past_key_values=cache, graph_decode=True, **kw, **extra)
 
-    tag = "fuyu-graph (int8, StaticKVCache, graph replay, 3 beams, prompt %d)" % a.fuyu_prompt
-    result[tag] = measure(tag, call, a.new, a.rounds, say)
+        tag = "fuyu-graph (int8, StaticKVCache, graph replay, 3 beams, prompt %d)" % a.fuyu_prompt
+        if switch in ("select", "sample"):
+            tag = "%s: fuyu-graph (int8, StaticKVCache, graph replay, no beams, one row, prompt %d)" % (switch, a.fuyu_prompt)
+        result[tag] = measure(tag, call, a.new, a.rounds, say)
     del model, cache
     gc.collect()
     torch.cuda.empty_cache()
@@ -181,11 +253,9 @@ def main():
     ap.add_argument("--fuyu-prompt", type=int, default=1350)
     ap.add_argument("--fuyu-layers", type=int, default=36)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--switch", choices=tuple(SWITCH_VAR), default="logits")
+    ap.add_argument("--switch", nargs="+", choices=tuple(SWITCH_VAR), default=["logits"])
     ap.add_argument("--b8", action=argparse.BooleanOptionalAction, default=True)
     a = ap.parse_args()
-    global switch
-    switch = a.switch
     if not torch.cuda.is_available():
         raise SystemExit("generate_e2e_bench: no GPU visible (this tool measures; it has no CPU mode)")
     if a.rounds < 3:
@@ -205,8 +275,9 @@ def main():
 
     dev = torch.cuda.get_device_properties(0)
     say("device: %s, %d CUs; torch %s" % (dev.name, dev.multi_processor_count, torch.__version__))
-    say("whole generate() calls, %s in the clock; paths: host (%s=0, the Python loop) | kernel (%s); %d rounds, alternating"
-        % (WHAT[switch], SWITCH_VAR[switch], {"logits": "otter_logits_process", "beam": "otter_beam_step"}[switch], a.rounds))
+    for sw in a.switch:
+        say("whole generate() calls, %s in the clock; paths: host (%s) | kernel (%s); %d rounds, alternating"
+            % (WHAT[sw], "the host sampler" if sw == "sample" else SWITCH_VAR[sw] + "=0, the host code", SYMBOL[sw], a.rounds))
     result = {}
     if "mpt" in a.points:
         mpt_points(a, say, result)
@@ -214,11 +285,17 @@ def main():
     if "fuyu" in a.points:
         fuyu_points(a, say, result)
     misses = sum(1 for r in result.values() if r["kernel_over_host"] > THRESHOLD)
-    differ = sum(1 for r in result.values() if not (r["tokens_equal"] or r.get("tokens_equal_under_tie_rule")))
-    explained = sum(1 for r in result.values() if not r["tokens_equal"] and r.get("tokens_equal_under_tie_rule"))
-    if explained:
-        say("points whose tokens differ from torch.topk's at a tie and equal the host block's under the stated tie rule: %d" % explained)
-    say("points with a MISS: %d of %d; points whose tokens differ: %d" % (misses, len(result), differ))
+    ok = lambda r: r["tokens_equal"] or r.get("tokens_equal_under_tie_rule") or r.get("tokens_equal_restatement")
+    differ = sum(1 for r in result.values() if not ok(r))
+    by_topk = sum(1 for r in result.values() if not r["tokens_equal"] and r.get("tokens_equal_under_tie_rule"))
+    by_rule = sum(1 for r in result.values() if not r["tokens_equal"] and r.get("tokens_equal_restatement"))
+    if by_topk:
+        say("beam points whose tokens differ from torch.topk's at a tie and equal the host block's under the stated tie rule: %d" % by_topk)
+    if by_rule:
+        say("sample points whose tokens differ from the host sampler's and equal the torch restatement of the kernel's rule over the same draws: %d"
+            % by_rule)
+    say("points with a MISS: %d of %d; points whose tokens differ from the host path's: %d, of them not accounted for above: %d"
+        % (misses, len(result), sum(1 for r in result.values() if not r["tokens_equal"]), differ))
     say(json.dumps(result))
     write_out()
     if differ:
