@@ -191,7 +191,8 @@ int otter_gemm_set_cu_budget(int cus);
 int otter_gemm_set_persistent(int on);
 /* Diagnostics and A/B switches of the GEMM kernels, one word.  Never set by the product path.
  *   bits 0-1  roofline ablations (results are WRONG): bit0 = no global loads inside the K loop, bit1 = no MFMAs
- *   bit 4 / 6 masked (edge-tile) tail on every tile / tile-phase timeline stamps (otter_gemm_read_timeline); bit 8: 4-wide fused tail
+ *   bit 4     timing ablation (results are WRONG: C is not written): every tile takes the masked (edge-tile) tail, which then skips its
+ *             global loads and stores;  bit 6: tile-phase timeline stamps (otter_gemm_read_timeline);  bit 8: 4-wide fused tail
  *   bits 9-13 tile order of the large-grid kernel (super-tile shape, walk direction; bit 13 = one workgroup per tile)
  *   bits 14-15 (round 6) cross-tile ring of the large-grid kernel: 0 = process default (on; env OTTER_GEMM_XT), 1 = off, 2 = on
  *   bits 16-22 + bit 23 (round 6): with bit 23 set, bits 16-22 replace the K-tile order of a tile (default 3 = rotated by the tile's N panel;
