@@ -508,6 +508,43 @@ int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t
                                     int64_t S_max, int64_t head_dim, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_decode_attn_cached_shared / otter_decode_attn_cached_shared_dyn -- otter_decode_attn_cached / _dyn for beam search over a
+ * SHARED PROMPT (otter_amd/kv_cache.py, StaticKVCache.share_prompt): the N rows are N / group sentences x `group` beams, the beams of a
+ * sentence contiguous, and keys [0, shared_len) of every beam are those of the sentence's first row (the leader, row (n / group) * group).
+ *   group    rows per sentence: 2 .. OTTER_DECODE_CACHED_SHARED_MAX_GROUP (one compiled instance each); N must be a multiple of it.
+ *   shared_len  a host scalar, 1 <= shared_len <= pos (dyn: 1 <= shared_len < S_max; a position below shared_len read from pos_dev makes
+ *            the call a no-op, like one outside [1, S_max)).  Constant over a generate() call, so it may sit in a captured launch.
+ *   src      as in otter_decode_attn_cached, but columns < shared_len are NOT read (they count as (n / group) * group).
+ *   workspace  at least OTTER_DECODE_CACHED_SHARED_WORKSPACE_BYTES(N, H, pos + 1) bytes (dyn: ..._SHARED_DYN_...(N, H, S_max)).
+ * The result is what otter_decode_attn_cached returns for a table whose columns [0, shared_len) hold (n / group) * group (the same
+ * arithmetic per key; the key ranges are split for N / group * H workgroups per range, so the fixed-order sums may group differently),
+ * and the written slot [n, h, pos] of every row n is bit-equal to that entry point's.  One workgroup serves a (key range, head, sentence):
+ * a key below shared_len is loaded once, from the leader's row, for all `group` queries.  No workgroup reads a slot this call writes:
+ * writes are slot pos of every row, reads through src are of keys < pos, shared reads of keys < shared_len <= pos.  Every other argument,
+ * the fixed-order reductions (two calls on the same inputs give the same bits) and the relation of the pair (at every pos in
+ * [shared_len, S_max) the _dyn entry gives the bits of the scalar entry) are as documented for otter_decode_attn_cached / _dyn.
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_DECODE_CACHED_SHARED_MAX_GROUP 6
+#define OTTER_DECODE_CACHED_SHARED_WORKSPACE_BYTES(N, H, Sk) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(Sk) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_shared(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                    int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                    const float* cos_rows, const float* sin_rows, int64_t cos_row_stride, void* k_cache,
+                                    int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                    int64_t v_cache_head_stride, const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid,
+                                    int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes,
+                                    int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim, float scale, int64_t group,
+                                    int64_t shared_len, void* stream);
+#define OTTER_DECODE_CACHED_SHARED_DYN_WORKSPACE_BYTES(N, H, S_max) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(S_max) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_shared_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                        int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                        const float* cos_table, const float* sin_table, int64_t table_row_stride, void* k_cache,
+                                        int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                        int64_t v_cache_head_stride, const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid,
+                                        int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace,
+                                        int64_t workspace_bytes, int64_t N, int64_t H, const int32_t* pos_dev, int64_t S_max, int64_t head_dim,
+                                        float scale, int64_t group, int64_t shared_len, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * otter_xattn_decode -- the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
  * head_dim 64: N rows (batch x beams) of ONE query each attend over the projected media of their sentence.
  *   q        bf16 [N, H * 64] with a row stride (elements, a multiple of 8, >= H * 64), 16-byte aligned.

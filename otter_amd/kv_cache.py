@@ -56,12 +56,37 @@ between calls.  Its step is `attend_persimmon`: csrc/persimmon_decode_cache.hip 
 mode) on the GPU in bf16 -- the arithmetic of csrc/persimmon_decode.hip line for line, so the static cache returns the default cache's
 tokens there -- and `attend_persimmon_reference` everywhere else.  The layout, the table, replay mode and the in-place invariant are the
 ones above; an int8 cache at head_dim 64 is not built (`NotImplementedError`).
+
+A shared prompt (`share_prompt(group)` on the empty cache; `generate(..., num_beams=nb, cache_implementation="static", share_prompt=True)`):
+under beam search the rows are sentences x `group` beams, the beams of a sentence contiguous, and every beam of a sentence carries the same
+prompt.  The prompt pass then runs one row per sentence and `fill` writes its keys and values into the sentence's first row only (the
+LEADER, row (n // group) * group):
+
+    group       rows per sentence (1: no sharing); `rows % group == 0`.
+    shared_len  the positions [0, shared_len) that every row reads from its leader: 0 until `fill`, then the prompt length.
+    src         src[n, :shared_len] = (n // group) * group, the row's own index elsewhere; created by `fill`, so no later than the first
+                cached step (and before `enable_replay`, which must find it: its address is fixed before capture).
+
+`reorder` is unchanged: beam search never moves a row to another sentence (the precondition; checked where the index is a CPU tensor), so the
+prefix columns stay on the leader whatever the ancestry.  `attend_reference`, `to_legacy` and the int8 kernels read through the table as they
+are.  In bf16 at head_dim 128 `attend` takes csrc/decode_cache_shared.hip (`ops.decode_attn_cached_shared`, `_dyn` in replay mode) for the
+group sizes it is built for, from SHARED_KERNEL_MIN_KEYS = 1 536 shared keys per head on (sentences x shared_len; below that the step is
+latency-bound and the table path is as fast or faster): one workgroup carries the `group` queries of a sentence and loads each shared key
+once.  OTTER_SHARED_PREFIX=0 keeps the table path (the A/B lever, like OTTER_HIP_BEAM) and =1 takes the kernel below the threshold too; other
+group sizes and the int8 cache stay on the table path, so the int8 form gets the saving of the prompt pass only.  The layout and the
+allocation stay as they are: the non-leader rows' slots [0, shared_len) are allocated and never touched, so sharing saves prompt-pass work
+and key / value traffic, not cache memory.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
+
+
+# a shared prompt: the grouped kernel from this many shared keys per head on (sentences x shared_len); measured, DESIGN.md 4.19
+SHARED_KERNEL_MIN_KEYS = 1536
 
 
 def rotate_half(x: torch.Tensor) -> torch.Tensor:
@@ -118,6 +143,7 @@ class StaticKVCache:
         self.pos_dev: Optional[torch.Tensor] = None     # replay mode (enable_replay)
         self.valid: Optional[torch.Tensor] = None
         self.kernel_steps = True        # replay mode: every `attend` so far ran on the dyn kernel (what a captured step needs)
+        self.group, self.shared_len = 1, 0              # a shared prompt (share_prompt)
 
     # ---- bookkeeping ----------------------------------------------------------------------------------------------------------------
 
@@ -153,7 +179,10 @@ class StaticKVCache:
         """The two things a forward may do with this cache: prefill it while empty, or append one position."""
         if torch.is_grad_enabled():
             raise RuntimeError("StaticKVCache is written in place and is for inference only: run the forward under torch.no_grad()")
-        if rows != self.rows:
+        if rows != self.rows and not (self.group > 1 and self.length == 0 and rows == self.rows // self.group):
+            if self.group > 1 and self.length == 0:
+                raise ValueError("StaticKVCache shares the prompt among groups of %d rows: the prompt pass has %d rows (one per group), "
+                                 "the forward has %d" % (self.group, self.rows // self.group, rows))
             raise ValueError("StaticKVCache was created for %d rows, the forward has %d" % (self.rows, rows))
         if self.length > 0 and S != 1:
             raise ValueError("StaticKVCache holds %d positions: only a one-token step can follow (got %d tokens)" % (self.length, S))
@@ -183,26 +212,47 @@ class StaticKVCache:
         self.pos_dev = None
         self.valid = None
         self.kernel_steps = True
+        self.group, self.shared_len = 1, 0
         self.rotary_tables = None       # (the Persimmon host keeps the tables a replay-mode step reads here: otter_amd/fuyu.py)
+
+    def share_prompt(self, group: int) -> None:
+        """On the empty cache: the rows are sentences x `group` contiguous beams that share their prompt (module docstring).  The prompt pass
+        then has rows // group rows, whose keys and values `fill` writes into the leaders' rows."""
+        group = int(group)
+        if self.length != 0 or self.replay:
+            raise ValueError("StaticKVCache.share_prompt: the cache is not empty")
+        if group < 1 or self.rows % group != 0:
+            raise ValueError("StaticKVCache.share_prompt: %d rows are not whole groups of %d" % (self.rows, group))
+        self.group, self.shared_len = group, 0
+
+    def _shared_table(self, S: int) -> torch.Tensor:
+        src = self._own_rows()
+        src[:, :S] = (torch.arange(self.rows, dtype=torch.int32, device=self.device) // self.group * self.group).view(-1, 1)
+        return src
 
     def fill(self, layer: int, k: torch.Tensor, v: torch.Tensor) -> None:
         """Prefill: k, v indexed [rows, n_heads, S, head_dim] (any strides: the views the flash and SDPA paths produce) -> positions [0, S).
         One strided copy per tensor.  int8: the prompt's vectors are rounded to the compute dtype first, so that the quantiser sees what
-        the unquantised cache would hold."""
+        the unquantised cache would hold.  A shared prompt (`share_prompt(group)`, group > 1): k, v [rows // group, n_heads, S, head_dim]
+        go into the leaders' rows 0, group, 2 group, ... only, shared_len <- S, and the table that points every row's columns [0, S) at
+        its leader is created."""
         if self.length != 0:
             raise ValueError("StaticKVCache.fill: the cache is not empty")
         S = k.shape[2]
-        want = (self.rows, self.n_heads, S, self.head_dim)
+        want = (self.rows // self.group, self.n_heads, S, self.head_dim)
         if tuple(k.shape) != want or tuple(v.shape) != want or S > self.max_len:
             raise ValueError("StaticKVCache.fill: expected k, v %s with S <= %d, got %s / %s" % (want, self.max_len, tuple(k.shape), tuple(v.shape)))
+        g = self.group                                   # (rows 0, g, 2 g, ...: every row when nothing is shared)
+        if g > 1 and self.shared_len != S:
+            self.shared_len, self.src = S, self._shared_table(S)
         if self.int8:
             for codes, scales, t in ((self.k, self.k_scale, k), (self.v, self.v_scale, v)):
                 c, s = quantize_kv_int8(t.to(self.dtype))
-                codes[layer, :, :, :S].copy_(c)
-                scales[layer, :, :, :S].copy_(s)
+                codes[layer, ::g, :, :S].copy_(c)
+                scales[layer, ::g, :, :S].copy_(s)
             return
-        self.k[layer, :, :, :S].copy_(k)
-        self.v[layer, :, :, :S].copy_(v)
+        self.k[layer, ::g, :, :S].copy_(k)
+        self.v[layer, ::g, :, :S].copy_(v)
 
     # ---- replay mode -----------------------------------------------------------------------------------------------------------------
 
@@ -217,6 +267,8 @@ class StaticKVCache:
             raise ValueError("StaticKVCache.enable_replay: replay mode is enabled already")
         if self.length < 1:
             raise ValueError("StaticKVCache.enable_replay: the cache is empty (the prompt pass fills it)")
+        if self.group > 1 and (self.src is None or self.shared_len != self.length):
+            raise ValueError("StaticKVCache.enable_replay: the prompt is shared but `fill` has not laid the table over it")
         if attention_mask is not None and tuple(attention_mask.shape) != (self.rows, self.length):
             raise ValueError("StaticKVCache.enable_replay: attention_mask must be [%d, %d], got %s"
                              % (self.rows, self.length, tuple(attention_mask.shape)))
@@ -252,7 +304,15 @@ class StaticKVCache:
         return torch.arange(self.rows, dtype=torch.int32, device=self.device).view(-1, 1).repeat(1, self.max_len)
 
     def reorder(self, beam_idx: torch.Tensor) -> None:
-        """Beam search: sequence n continues what was sequence beam_idx[n].  Only the table moves (rows x length x 4 bytes), in place."""
+        """Beam search: sequence n continues what was sequence beam_idx[n].  Only the table moves (rows x length x 4 bytes), in place.
+        A shared prompt: the precondition is that beam_idx[n] is a row of n's own sentence (beam search never moves a row to another
+        sentence) -- then columns [0, shared_len) stay on the leader and the arithmetic is the same.  It is checked where beam_idx is a
+        CPU tensor (ValueError); an index on the GPU is not read back."""
+        if self.group > 1 and not beam_idx.is_cuda:
+            own = torch.arange(self.rows) // self.group
+            if beam_idx.numel() != self.rows or not torch.equal(beam_idx.reshape(-1).long() // self.group, own):
+                raise ValueError("StaticKVCache.reorder: with a shared prompt every row must continue a row of its own group of %d "
+                                 "(beam_idx %s)" % (self.group, beam_idx.reshape(-1).tolist()))
         if self.src is None:
             if self.replay:
                 raise ValueError("StaticKVCache.reorder: replay mode was enabled without beams (the table cannot appear after capture)")
@@ -292,6 +352,21 @@ class StaticKVCache:
     def uses_kernel(self, q: torch.Tensor, n_kv: int) -> bool:
         return q.is_cuda and q.dtype == torch.bfloat16 and self.dtype == torch.bfloat16 and self.head_dim == 128 and n_kv == q.shape[1]
 
+    def uses_shared_kernel(self, q: torch.Tensor, n_kv: int) -> bool:
+        """The step runs on csrc/decode_cache_shared.hip: a shared prompt in a group size the kernel is built for, a bf16 cache where
+        `uses_kernel` holds, and OTTER_SHARED_PREFIX != "0" (the A/B lever: "0" keeps the existing kernel, through the table).  Unless the
+        lever is "1" the kernel is taken only from SHARED_KERNEL_MIN_KEYS shared keys per head on (sentences x shared_len): below that the
+        step is bound by latency and the grouped kernel, with a third of the workgroups, measured 3.5 % slower.  All of this
+        is fixed for a whole generate call, so a captured step keeps its kernel."""
+        lever = os.environ.get("OTTER_SHARED_PREFIX", "")
+        if self.group < 2 or self.shared_len < 1 or self.int8 or lever == "0":
+            return False
+        if lever != "1" and (self.rows // self.group) * self.shared_len < SHARED_KERNEL_MIN_KEYS:
+            return False
+        from . import ops
+
+        return self.group in ops.DECODE_CACHED_SHARED_GROUPS and self.uses_kernel(q, n_kv)
+
     def attend(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
         """One cached step of `layer` at position `length` (which the caller advances once per forward, after the last layer):
         q [N,H,d], k_new / v_new [N,H_kv,d] views of the projection output; cos / sin fp32 [d] rows of that position or None;
@@ -308,6 +383,10 @@ class StaticKVCache:
                     return ops.decode_attn_cached_i8_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
                                                          self.pos_dev, scale, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
                                                          slopes=slopes)
+                if self.uses_shared_kernel(q, k_new.shape[1]):
+                    return ops.decode_attn_cached_shared_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.pos_dev, scale, self.group,
+                                                             self.shared_len, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
+                                                             slopes=slopes)
                 return ops.decode_attn_cached_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.pos_dev, scale, cos_table=cos,
                                                   sin_table=sin, src=self.src, key_valid=self.valid, slopes=slopes)
             self.kernel_steps = False   # (the restatement reads the position back to the host: such a step cannot be captured)
@@ -318,6 +397,9 @@ class StaticKVCache:
             if self.int8:
                 return ops.decode_attn_cached_i8(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
                                                  self.length, scale, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)
+            if self.uses_shared_kernel(q, k_new.shape[1]):
+                return ops.decode_attn_cached_shared(q, k_new, v_new, self.k[layer], self.v[layer], self.length, scale, self.group,
+                                                     self.shared_len, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)
             return ops.decode_attn_cached(q, k_new, v_new, self.k[layer], self.v[layer], self.length, scale, cos=cos, sin=sin, src=self.src,
                                           key_valid=key_valid, slopes=slopes)
         return self.attend_reference(layer, q, k_new, v_new, scale, cos=cos, sin=sin, key_valid=key_valid, slopes=slopes)

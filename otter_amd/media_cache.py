@@ -100,6 +100,20 @@ class MediaCache:
             kv = F.linear(med.to(cd), Wkv.detach().to(cd))
         return kv.view(S, T_img * n, Wkv.shape[0])
 
+    def expand(self, beams: int) -> None:
+        """After a prompt pass that ran one row per sentence (`generate(..., share_prompt=True)`): every row becomes `beams` contiguous rows
+        of the same sentence.  The counts are repeated; kv, one copy per sentence already, is untouched.  Before `fixed_address` is set
+        (`seen` is replaced here) and before any cached step."""
+        beams = int(beams)
+        if not self.filled:
+            raise ValueError("MediaCache.expand: the cache is empty (the prompt pass fills it)")
+        if self.rows_per_media != 1 or self.fixed_address:
+            raise ValueError("MediaCache.expand: only a cache of one row per sentence that no captured graph reads can be expanded")
+        if beams < 1:
+            raise ValueError("MediaCache.expand: beams >= 1 (got %d)" % beams)
+        self.seen = self.seen.repeat_interleave(beams)
+        self.rows, self.rows_per_media = self.sentences * beams, beams
+
     def advance(self, new_ids: torch.Tensor) -> torch.Tensor:
         """One step: new_ids [rows] or [rows, 1].  Returns the step's text_time, int32 [rows] (the cache's own tensor)."""
         if not self.filled:

@@ -673,14 +673,21 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             if not use_cache:
                 raise ValueError("generate: cross_attention_cache=True needs use_cache=True or cache_implementation='static'")
             media[0] = False                                 # (wanted, not created yet)
+        share = bool(generate_kwargs.pop("share_prompt", False))
+        if share and not (static and num_beams > 1):
+            raise ValueError("generate: share_prompt=True needs cache_implementation='static' and num_beams > 1")
         graph_step = [None]                                  # the GraphDecodeStep of this call, created after the prompt pass
         generate_kwargs.setdefault("eos_token_id", self.eoc_token_id)
         self._encode_vision_x(vision_x=vision_x)
-        if num_beams > 1:   # perceiver output repeated per beam: same conditioning as encoding the repeated frames, 1/num_beams the work
-            for layer in self.lang_encoder._get_decoder_layers():
+        lm = self.lang_encoder
+
+        def repeat_vis_x():
+            for layer in lm._get_decoder_layers():
                 if layer.vis_x is not None:
                     layer.condition_vis_x(layer.vis_x.repeat_interleave(num_beams, dim=0))
-        lm = self.lang_encoder
+
+        if num_beams > 1 and not share:   # perceiver output repeated per beam: same conditioning as encoding the repeated frames, 1/num_beams the work
+            repeat_vis_x()
 
         def new_static_cache(ids):
             n_layers, n_kv, head_dim, host_max = cache_geometry(lm.config)
@@ -692,15 +699,32 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         def media_kw(ids, past, beam_idx):
             if media[0] is None:
                 return {}
-            if past is None:
+            if past is None and share:                   # the prompt pass has one row per sentence; `expand` follows it
+                media[0] = MediaCache(ids.shape[0] // num_beams, self.media_token_id, rows_per_media=1)
+            elif past is None:
                 media[0] = MediaCache(ids.shape[0], self.media_token_id, rows_per_media=num_beams)
             elif beam_idx is not None:
                 media[0].reorder(beam_idx)
             return {"media_cache": media[0]}
 
+        def shared_prompt_pass(ids, mask, mkw):
+            """share_prompt=True: generate_tokens has repeated the prompt per beam; the pass runs the sentences' first rows only, the gated
+            layers conditioned on the un-repeated perceiver output, and fills the leaders' rows of a cache of sentences x beams rows
+            (StaticKVCache.share_prompt).  Every beam then starts from its sentence's logits."""
+            past = new_static_cache(ids)
+            past.share_prompt(num_beams)
+            out = lm(input_ids=ids[::num_beams].contiguous(), attention_mask=mask[::num_beams].contiguous() if mask is not None else None,
+                     past_key_values=past, use_cache=True, **mkw)
+            if media[0] is not None:
+                media[0].expand(num_beams)                   # (before enable_replay and the GraphDecodeStep: `seen` is replaced)
+            repeat_vis_x()                                   # the legacy cached gated block still reads vis_x per row
+            return out.logits[:, -1, :].repeat_interleave(num_beams, dim=0), past
+
         def step(ids, mask, past, beam_idx):
             mkw = media_kw(ids, past, beam_idx)
             if static:
+                if past is None and share:
+                    return shared_prompt_pass(ids, mask, mkw)
                 if past is None:                             # rows = sentences x beams: generate_tokens has repeated the prompt already
                     return_ids, past = ids, new_static_cache(ids)
                 else:

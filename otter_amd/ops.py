@@ -813,7 +813,59 @@ def decode_attn_cached_i8_dyn(q, k_new, v_new, k_cache, v_cache, k_scale, v_scal
     return o
 
 
-XATTN_DECODE_MAX_KEYS = 65536          # include/otter_hip.h: M = T_img * n_per_media <= 65536
+DECODE_CACHED_SHARED_GROUPS = (2, 3, 4, 5, 6)     # include/otter_hip.h: 2 .. OTTER_DECODE_CACHED_SHARED_MAX_GROUP, one kernel instance each
+
+decode_attn_cached_shared_workspace_bytes = decode_attn_cached_shared_dyn_workspace_bytes = decode_attn_cached_workspace_bytes
+
+
+def _check_shared(name, dyn, N, group, shared_len, pos, S_max):
+    """The grouping of the shared-prompt entry points: `group` rows per sentence, `shared_len` leading keys read from the sentence's first
+    row.  `pos`: the position scalar (ignored with `dyn`).  Returns (group, shared_len) as ints."""
+    group, shared_len = int(group), int(shared_len)
+    if group not in DECODE_CACHED_SHARED_GROUPS:
+        raise K.OtterHipError(f"{name}: group={group}: the kernel is built for groups of {DECODE_CACHED_SHARED_GROUPS[0]} to "
+                              f"{DECODE_CACHED_SHARED_GROUPS[-1]} rows")
+    if N % group:
+        raise K.OtterHipError(f"{name}: N={N} rows are not whole groups of {group}")
+    if dyn:
+        if shared_len < 1 or shared_len >= S_max:
+            raise K.OtterHipError(f"{name}: shared_len={shared_len} outside [1, S_max) with S_max={S_max}")
+    elif shared_len < 1 or shared_len > pos:
+        raise K.OtterHipError(f"{name}: shared_len={shared_len} outside [1, pos] with pos={pos}")
+    return group, shared_len
+
+
+def decode_attn_cached_shared(q, k_new, v_new, k_cache, v_cache, pos, scale, group, shared_len, cos=None, sin=None, src=None, key_valid=None,
+                              slopes=None):
+    """decode_attn_cached for beam search over a shared prompt (otter_decode_attn_cached_shared): the N rows are sentences x `group` beams
+    (contiguous), and keys [0, shared_len) of every beam are read from the sentence's first row, once for the whole group -- what
+    decode_attn_cached returns for a table whose columns [0, shared_len) hold (n // group) * group; columns < shared_len of `src` are not
+    read.  group in DECODE_CACHED_SHARED_GROUPS, N % group == 0, 1 <= shared_len <= pos.  Everything else as decode_attn_cached.
+    Returns o [N,H*128] bf16."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, cos, sin, src, key_valid, slopes)
+    name = "decode_attn_cached_shared"
+    args, o = _decode_cached_args(name, False, q, k_new, v_new, k_cache, v_cache, None, pos, scale, cos, sin, src, key_valid, slopes, None)
+    grouping = _check_shared(name, False, q.shape[0], group, shared_len, int(pos), k_cache.shape[2])
+    K.check(K.lib().otter_decode_attn_cached_shared(*args, *grouping, K.stream()), name)
+    return o
+
+
+def decode_attn_cached_shared_dyn(q, k_new, v_new, k_cache, v_cache, pos_dev, scale, group, shared_len, cos_table=None, sin_table=None, src=None,
+                                  key_valid=None, slopes=None, out=None):
+    """decode_attn_cached_shared with the position in device memory (otter_decode_attn_cached_shared_dyn): every argument but `group` and
+    `shared_len` as decode_attn_cached_dyn; 1 <= shared_len < S_max, a host scalar that stays the same over a generate() call (a position
+    below it, like one outside [1, S_max), makes the call a no-op).  Returns o [N,H*128] bf16 (`out`: a contiguous bf16 [N,H*128] tensor
+    to write instead)."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, pos_dev, cos_table, sin_table, src, key_valid, slopes, out)
+    name = "decode_attn_cached_shared_dyn"
+    args, o = _decode_cached_args(name, True, q, k_new, v_new, k_cache, v_cache, None, pos_dev, scale, cos_table, sin_table, src, key_valid,
+                                  slopes, out)
+    grouping = _check_shared(name, True, q.shape[0], group, shared_len, None, k_cache.shape[2])
+    K.check(K.lib().otter_decode_attn_cached_shared_dyn(*args, *grouping, K.stream()), name)
+    return o
+
+
+XATTN_DECODE_MAX_KEYS = 65536         # include/otter_hip.h: M = T_img * n_per_media <= 65536
 
 
 def xattn_decode(q, k, v, H, text_time, n_per_media, rows_per_media, mask_mode, scale, out=None):
