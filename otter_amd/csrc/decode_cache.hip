@@ -21,25 +21,13 @@
 // depends on the position, so a captured graph of it can be replayed step after step.  Both derive the key ranges of a position from
 // split_rule (host and device); a workgroup of the dyn grid whose range index is not live at the current position returns before it touches
 // memory, and the combine kernel merges exactly the live ranges -- so at every position the two entry points give the same bits.
-#include "decode_split.h"
+#include "decode_cached_entry.h"
 
 namespace {
 
 constexpr int HD = 128, LANES = 16, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL;
 
-struct DcArgs {
-    const bf16_t* q; int64_t q_rs, q_hs;                  // new token: q / k / v [n, h, 128], row / head strides (elements), dim stride 1
-    const bf16_t* kn; int64_t kn_rs, kn_hs;
-    const bf16_t* vn; int64_t vn_rs, vn_hs;
-    const float *cs, *sn; int64_t cs_rs;                  // rotary row(s) of position pos, fp32 [128]; row stride 0 = shared; null = no rotary
-    bf16_t* kc; int64_t kc_rs, kc_hs;                     // cache [row, h, key, 128]: row / head strides, key stride 128
-    bf16_t* vc; int64_t vc_rs, vc_hs;
-    const int32_t* src; int64_t src_rs;                   // [N, >= pos] or null (= the row's own)
-    const uint8_t* kvalid; int64_t kv_rs;                 // [N, >= pos + 1] or null
-    const float* slopes;                                  // [H] or null
-    bf16_t* o;                                            // [N, H * 128]
-    float* part;                                          // [N * H * part_stride, PART] (nsplit > 1), part_stride >= nsplit
-    int N, H, pos, nsplit, kps, part_stride;
+struct DcArgs : Bf16StepArgs {                            // (decode_cached_entry.h: the new token, the cache, the tables, o, the ranges)
     float scale;
 };
 
@@ -128,11 +116,6 @@ __global__ __launch_bounds__(NT) void decode_cached_kernel(DcArgs a) {
     decode_cached_body(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
 }
 
-__global__ __launch_bounds__(HD) void decode_cached_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, nsplit);
-}
-
 // ---- the position in device memory (decode_split.h): grid (max_ranges, H, N) for the capacity --------------------------------------------
 __global__ __launch_bounds__(NT) void decode_cached_dyn_kernel(DcArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus, int64_t table_rs) {
     DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)a.N * a.H, cus);
@@ -142,48 +125,10 @@ __global__ __launch_bounds__(NT) void decode_cached_dyn_kernel(DcArgs a, const i
                        a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
 }
 
-__global__ __launch_bounds__(HD) void decode_cached_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
-                                                                       const int32_t* __restrict__ pos_dev, int N, int H, int S_max, int cus,
-                                                                       int max_ranges) {
-    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)N * H, cus);
-    const int nsplit = min(sp.nsplit, max_ranges);
-    if (nsplit == 1) return;                              // the one live workgroup wrote o itself
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
-}
-
-bool mult8(int64_t a, int64_t b) { return a % 8 == 0 && b % 8 == 0; }
-
 }  // namespace
 
-// the argument checks both entry points share (NAME: the entry point's name in messages).  Three macros where decode_cache_i8.hip has one:
-// here the scalar entry point checks `pos` between the shape and the alignment checks and the dyn one checks `pos_dev` between the alignment
-// and the stride checks, and the order of the checks is part of the ABI (the first failing check names the error).
-#define DC_REQUIRE_SHAPE(NAME)                                                                                    \
-    OTTER_REQUIRE(head_dim == HD, NAME ": head_dim %ld (128 only)", (long)head_dim);                             \
-    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, NAME ": bad shape N=%ld H=%ld", (long)N, (long)H);  \
-    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, NAME ": S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT)
-
-#define DC_REQUIRE_ALIGNED(NAME)                                                                                            \
-    OTTER_REQUIRE((((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0, \
-                  NAME ": q, k_new, v_new, k_cache, v_cache need 16-byte alignment")
-
-#define DC_REQUIRE_STRIDES(NAME)                                                                                                                    \
-    OTTER_REQUIRE(mult8(q_row_stride, q_head_stride) && mult8(k_new_row_stride, k_new_head_stride) && mult8(v_new_row_stride, v_new_head_stride) && \
-                      mult8(k_cache_row_stride, k_cache_head_stride) && mult8(v_cache_row_stride, v_cache_head_stride),                            \
-                  NAME ": q / k_new / v_new / cache strides must be multiples of 8 elements");                                                     \
-    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0,     \
-                  NAME ": a cache head stride below S_max * 128 would make the slots of two heads overlap")
-
-#define DC_FILL_ARGS(a)                                                                                                       \
-    a.q = (const bf16_t*)q; a.q_rs = q_row_stride; a.q_hs = q_head_stride;                                                    \
-    a.kn = (const bf16_t*)k_new; a.kn_rs = k_new_row_stride; a.kn_hs = k_new_head_stride;                                     \
-    a.vn = (const bf16_t*)v_new; a.vn_rs = v_new_row_stride; a.vn_hs = v_new_head_stride;                                     \
-    a.kc = (bf16_t*)k_cache; a.kc_rs = k_cache_row_stride; a.kc_hs = k_cache_head_stride;                                     \
-    a.vc = (bf16_t*)v_cache; a.vc_rs = v_cache_row_stride; a.vc_hs = v_cache_head_stride;                                     \
-    a.src = src; a.src_rs = src_row_stride; a.kvalid = key_valid; a.kv_rs = key_valid_row_stride; a.slopes = alibi_slopes;    \
-    a.o = (bf16_t*)o; a.part = (float*)workspace; a.N = (int)N; a.H = (int)H; a.scale = scale
-
+// (the order of the checks is ABI: the scalar entry point checks `pos` before the alignment checks, the dyn one `pos_dev` between the
+// alignment and the stride checks -- decode_cached_entry.h)
 extern "C" {
 
 int otter_decode_attn_cached(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
@@ -193,35 +138,24 @@ int otter_decode_attn_cached(const void* q, int64_t q_row_stride, int64_t q_head
                              const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride,
                              const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos,
                              int64_t S_max, int64_t head_dim, float scale, void* stream) {
-    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && o && workspace, "decode_attn_cached: null pointer");
-    OTTER_REQUIRE((cos_rows == nullptr) == (sin_rows == nullptr), "decode_attn_cached: cos_rows and sin_rows must both be given or both be NULL");
-    DC_REQUIRE_SHAPE("decode_attn_cached");
-    OTTER_REQUIRE(pos >= 1, "decode_attn_cached: pos=%ld: a cached step continues a cache (pos >= 1)", (long)pos);
-    OTTER_REQUIRE(pos < S_max, "decode_attn_cached: pos=%ld is beyond the cache capacity S_max=%ld", (long)pos, (long)S_max);
-    DC_REQUIRE_ALIGNED("decode_attn_cached");
-    DC_REQUIRE_STRIDES("decode_attn_cached");
-    OTTER_REQUIRE(cos_row_stride >= 0 && (!src || src_row_stride >= pos) && (!key_valid || key_valid_row_stride >= pos + 1),
-                  "decode_attn_cached: src needs a row stride >= pos, key_valid one >= pos + 1, cos / sin a non-negative one");
-    const int64_t Sk = pos + 1;
-    const int64_t need = OTTER_DECODE_CACHED_WORKSPACE_BYTES(N, H, Sk);
-    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "decode_attn_cached";
+    DcArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                  v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
+                 (bf16_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (bf16_t*)v_cache, v_cache_row_stride, v_cache_head_stride, src,
+                 src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                scale};
+    if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, o, workspace})) return e;
+    if (int e = require_cos_sin_pair(name, cos_rows, sin_rows, "rows")) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_position(name, pos, S_max)) return e;
+    if (int e = require_token_and_cache_aligned(name, a)) return e;
+    if (int e = require_cache_layout(name, &a, a, 8, S_max, HD)) return e;
+    if (int e = require_row_strides(name, a, &cos_row_stride, pos)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_WORKSPACE_BYTES(N, H, pos + 1))) return e;
 
-    const Split sp = split_rule<KEYS_PER_ITER>(Sk, N * H, cu_count());
-    const int64_t nsplit = sp.nsplit;
-
-    DcArgs a;
-    DC_FILL_ARGS(a);
-    a.cs = cos_rows; a.sn = sin_rows; a.cs_rs = cos_row_stride;
-    a.pos = (int)pos; a.nsplit = (int)nsplit; a.kps = sp.kps; a.part_stride = (int)nsplit;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(decode_cached_kernel, dim3((unsigned)nsplit, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a);
-    OTTER_CHECK_LAUNCH("decode_attn_cached");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(decode_cached_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o, (int)H,
-                           (int)nsplit);
-        OTTER_CHECK_LAUNCH("decode_attn_cached (combine)");
-    }
-    return OTTER_OK;
+    return launch_scalar<HD>(name, a, pos, split_rule<KEYS_PER_ITER>(pos + 1, N * H, cu_count()), N, stream,
+                             [](dim3 grid, hipStream_t st, const DcArgs& a) { hipLaunchKernelGGL(decode_cached_kernel, grid, dim3(NT), 0, st, a); });
 }
 
 int otter_decode_attn_cached_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
@@ -231,41 +165,29 @@ int otter_decode_attn_cached_dyn(const void* q, int64_t q_row_stride, int64_t q_
                                  int64_t v_cache_head_stride, const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid,
                                  int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes,
                                  int64_t N, int64_t H, const int32_t* pos_dev, int64_t S_max, int64_t head_dim, float scale, void* stream) {
-    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && o && workspace && pos_dev, "decode_attn_cached_dyn: null pointer");
-    OTTER_REQUIRE((cos_table == nullptr) == (sin_table == nullptr),
-                  "decode_attn_cached_dyn: cos_table and sin_table must both be given or both be NULL");
-    DC_REQUIRE_SHAPE("decode_attn_cached_dyn");
-    DC_REQUIRE_ALIGNED("decode_attn_cached_dyn");
-    OTTER_REQUIRE(((uintptr_t)pos_dev & 3) == 0, "decode_attn_cached_dyn: pos_dev needs 4-byte alignment");
-    DC_REQUIRE_STRIDES("decode_attn_cached_dyn");
-    // any position below S_max may be read from pos_dev: the tables, the beam table and the mask must hold the capacity
-    OTTER_REQUIRE((!cos_table || table_row_stride >= HD) && (!src || src_row_stride >= S_max - 1) && (!key_valid || key_valid_row_stride >= S_max),
-                  "decode_attn_cached_dyn: cos / sin tables need a row stride >= 128, src one >= S_max - 1, key_valid one >= S_max");
-    const int64_t need = OTTER_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max);
-    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "decode_attn_cached_dyn";
+    DcArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                  v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
+                 (bf16_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (bf16_t*)v_cache, v_cache_row_stride, v_cache_head_stride, src,
+                 src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                scale};
+    if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, o, workspace, pos_dev})) return e;
+    if (int e = require_cos_sin_pair(name, cos_table, sin_table, "table")) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_token_and_cache_aligned(name, a)) return e;
+    if (int e = require_pos_dev_aligned(name, pos_dev)) return e;
+    if (int e = require_cache_layout(name, &a, a, 8, S_max, HD)) return e;
+    if (int e = require_table_strides(name, a, table_row_stride, HD, "128", S_max)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max))) return e;
 
     const int cus = cu_count();
-    const int64_t max_ranges = split_max_ranges(S_max, N * H, cus);
-
-    DcArgs a;
-    DC_FILL_ARGS(a);
-    a.cs = cos_table; a.sn = sin_table; a.cs_rs = 0;
-    a.pos = 0; a.nsplit = 0; a.kps = 0; a.part_stride = (int)max_ranges;   // (pos, nsplit, kps: read and derived on the device)
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(decode_cached_dyn_kernel, dim3((unsigned)max_ranges, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a, pos_dev, (int)S_max, cus,
-                       table_row_stride);
-    OTTER_CHECK_LAUNCH("decode_attn_cached_dyn");
-    if (max_ranges > 1) {
-        hipLaunchKernelGGL(decode_cached_dyn_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o,
-                           pos_dev, (int)N, (int)H, (int)S_max, cus, (int)max_ranges);
-        OTTER_CHECK_LAUNCH("decode_attn_cached_dyn (combine)");
-    }
-    return OTTER_OK;
+    const DynStep d = {pos_dev, (int)S_max, cus, (int)split_max_ranges(S_max, N * H, cus), table_row_stride};
+    return launch_dyn(name, a, d, N, stream,
+                      [](dim3 grid, hipStream_t st, const DcArgs& a, const DynStep& d) {
+                          hipLaunchKernelGGL(decode_cached_dyn_kernel, grid, dim3(NT), 0, st, a, d.pos_dev, d.S_max, d.cus, d.table_rs);
+                      },
+                      DynCombine<HD, KEYS_PER_ITER>());
 }
 
 }  // extern "C"
-
-#undef DC_REQUIRE_SHAPE
-#undef DC_REQUIRE_ALIGNED
-#undef DC_REQUIRE_STRIDES
-#undef DC_FILL_ARGS

@@ -17,17 +17,13 @@
 // 16 l8 .. 16 l8 + 15, one 16-byte load each of K and V codes; the key's two scales are one 4-byte load each, the same address in all 8 lanes),
 // 32 groups, two keys per group in flight = 64 keys per iteration: s = k_scale * sum q[i] code_k[i] by an 8-lane butterfly, online softmax per
 // group, acc += (p * v_scale) * code_v[i].
-#include "decode_split.h"
+#include "decode_cached_entry.h"
 
 namespace {
 
 constexpr int HD = 128, LANES = 8, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL, DPL = HD / LANES;
 
-struct DqArgs {
-    const bf16_t* q; int64_t q_rs, q_hs;                  // new token: q / k / v [n, h, 128], row / head strides (elements), dim stride 1
-    const bf16_t* kn; int64_t kn_rs, kn_hs;
-    const bf16_t* vn; int64_t vn_rs, vn_hs;
-    const float *cs, *sn; int64_t cs_rs;                  // rotary row(s) of position pos, fp32 [128]; row stride 0 = shared; null = no rotary
+struct DqArgs : NewTokenArgs {                            // (decode_cached_entry.h: q / k / v of the new token, the rotary rows)
     int8_t* kc; int64_t kc_rs, kc_hs;                     // codes [row, h, key, 128]: row / head strides, key stride 128
     int8_t* vc; int64_t vc_rs, vc_hs;
     float* ks; int64_t ks_rs, ks_hs;                      // scales [row, h, key]: row / head strides, key stride 1
@@ -194,11 +190,6 @@ __global__ __launch_bounds__(NT) void decode_cached_i8_kernel(DqArgs a) {
     decode_cached_i8_body(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
 }
 
-__global__ __launch_bounds__(HD) void decode_cached_i8_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, nsplit);
-}
-
 // ---- the position in device memory (decode_split.h): grid (max_ranges, H, N) for the capacity --------------------------------------------
 __global__ __launch_bounds__(NT) void decode_cached_i8_dyn_kernel(DqArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus,
                                                                   int64_t table_rs) {
@@ -209,48 +200,21 @@ __global__ __launch_bounds__(NT) void decode_cached_i8_dyn_kernel(DqArgs a, cons
                           a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
 }
 
-__global__ __launch_bounds__(HD) void decode_cached_i8_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
-                                                                          const int32_t* __restrict__ pos_dev, int N, int H, int S_max, int cus,
-                                                                          int max_ranges) {
-    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)N * H, cus);
-    const int nsplit = min(sp.nsplit, max_ranges);
-    if (nsplit == 1) return;                              // the one live workgroup wrote o itself
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
+// the two checks of the scales: their alignment follows the codes', their head strides the codes'
+int require_scales_aligned(const char* name, const DqArgs& a) {
+    OTTER_REQUIRE((((uintptr_t)a.ks | (uintptr_t)a.vs) & 3) == 0, "%s: k_scale, v_scale need 4-byte alignment", name);
+    return OTTER_OK;
 }
 
-bool mult(int64_t m, int64_t a, int64_t b) { return a % m == 0 && b % m == 0; }
+int require_scale_head_strides(const char* name, const DqArgs& a, int64_t S_max) {
+    OTTER_REQUIRE(a.ks_hs >= S_max && a.vs_hs >= S_max && a.ks_rs >= 0 && a.vs_rs >= 0,
+                  "%s: a scale head stride below S_max would make the scales of two heads overlap", name);
+    return OTTER_OK;
+}
 
 }  // namespace
 
-// the argument checks both entry points share (NAME: the entry point's name in messages)
-#define DQ_REQUIRE_COMMON(NAME)                                                                                                                       \
-    OTTER_REQUIRE(head_dim == HD, NAME ": head_dim %ld (128 only)", (long)head_dim);                                                                 \
-    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, NAME ": bad shape N=%ld H=%ld", (long)N, (long)H);                                      \
-    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, NAME ": S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT);                           \
-    OTTER_REQUIRE((((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,                         \
-                  NAME ": q, k_new, v_new, k_cache, v_cache need 16-byte alignment");                                                                \
-    OTTER_REQUIRE((((uintptr_t)k_scale | (uintptr_t)v_scale) & 3) == 0, NAME ": k_scale, v_scale need 4-byte alignment");                             \
-    OTTER_REQUIRE(mult(8, q_row_stride, q_head_stride) && mult(8, k_new_row_stride, k_new_head_stride) && mult(8, v_new_row_stride, v_new_head_stride), \
-                  NAME ": q / k_new / v_new strides must be multiples of 8 elements");                                                               \
-    OTTER_REQUIRE(mult(16, k_cache_row_stride, k_cache_head_stride) && mult(16, v_cache_row_stride, v_cache_head_stride),                             \
-                  NAME ": code cache strides must be multiples of 16 elements");                                                                     \
-    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0,       \
-                  NAME ": a cache head stride below S_max * 128 would make the slots of two heads overlap");                                         \
-    OTTER_REQUIRE(k_scale_head_stride >= S_max && v_scale_head_stride >= S_max && k_scale_row_stride >= 0 && v_scale_row_stride >= 0,                 \
-                  NAME ": a scale head stride below S_max would make the scales of two heads overlap")
-
-#define DQ_FILL_ARGS(a)                                                                                                       \
-    a.q = (const bf16_t*)q; a.q_rs = q_row_stride; a.q_hs = q_head_stride;                                                    \
-    a.kn = (const bf16_t*)k_new; a.kn_rs = k_new_row_stride; a.kn_hs = k_new_head_stride;                                     \
-    a.vn = (const bf16_t*)v_new; a.vn_rs = v_new_row_stride; a.vn_hs = v_new_head_stride;                                     \
-    a.kc = (int8_t*)k_cache; a.kc_rs = k_cache_row_stride; a.kc_hs = k_cache_head_stride;                                     \
-    a.vc = (int8_t*)v_cache; a.vc_rs = v_cache_row_stride; a.vc_hs = v_cache_head_stride;                                     \
-    a.ks = k_scale; a.ks_rs = k_scale_row_stride; a.ks_hs = k_scale_head_stride;                                              \
-    a.vs = v_scale; a.vs_rs = v_scale_row_stride; a.vs_hs = v_scale_head_stride;                                              \
-    a.src = src; a.src_rs = src_row_stride; a.kvalid = key_valid; a.kv_rs = key_valid_row_stride; a.slopes = alibi_slopes;    \
-    a.o = (bf16_t*)o; a.part = (float*)workspace; a.N = (int)N; a.H = (int)H; a.scale = scale
-
+// (here the position's check, `pos` or `pos_dev`, follows every check of the layout: the order of this file's entry points since they exist)
 extern "C" {
 
 int otter_decode_attn_cached_i8(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
@@ -262,34 +226,27 @@ int otter_decode_attn_cached_i8(const void* q, int64_t q_row_stride, int64_t q_h
                                 const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace,
                                 int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim, float scale,
                                 void* stream) {
-    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && k_scale && v_scale && o && workspace, "decode_attn_cached_i8: null pointer");
-    OTTER_REQUIRE((cos_rows == nullptr) == (sin_rows == nullptr),
-                  "decode_attn_cached_i8: cos_rows and sin_rows must both be given or both be NULL");
-    DQ_REQUIRE_COMMON("decode_attn_cached_i8");
-    OTTER_REQUIRE(pos >= 1, "decode_attn_cached_i8: pos=%ld: a cached step continues a cache (pos >= 1)", (long)pos);
-    OTTER_REQUIRE(pos < S_max, "decode_attn_cached_i8: pos=%ld is beyond the cache capacity S_max=%ld", (long)pos, (long)S_max);
-    OTTER_REQUIRE(cos_row_stride >= 0 && (!src || src_row_stride >= pos) && (!key_valid || key_valid_row_stride >= pos + 1),
-                  "decode_attn_cached_i8: src needs a row stride >= pos, key_valid one >= pos + 1, cos / sin a non-negative one");
-    const int64_t Sk = pos + 1;
-    const int64_t need = OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES(N, H, Sk);
-    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_i8: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "decode_attn_cached_i8";
+    DqArgs a = {{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                 v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
+                (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
+                k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
+                src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H};
+    a.scale = scale;
+    if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, o, workspace})) return e;
+    if (int e = require_cos_sin_pair(name, cos_rows, sin_rows, "rows")) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_token_and_cache_aligned(name, a)) return e;
+    if (int e = require_scales_aligned(name, a)) return e;
+    if (int e = require_cache_layout(name, &a, a, 16, S_max, HD)) return e;
+    if (int e = require_scale_head_strides(name, a, S_max)) return e;
+    if (int e = require_position(name, pos, S_max)) return e;
+    if (int e = require_row_strides(name, a, &cos_row_stride, pos)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_I8_WORKSPACE_BYTES(N, H, pos + 1))) return e;
 
-    const Split sp = split_rule<KEYS_PER_ITER>(Sk, N * H, cu_count());
-    const int64_t nsplit = sp.nsplit;
-
-    DqArgs a;
-    DQ_FILL_ARGS(a);
-    a.cs = cos_rows; a.sn = sin_rows; a.cs_rs = cos_row_stride;
-    a.pos = (int)pos; a.nsplit = (int)nsplit; a.kps = sp.kps; a.part_stride = (int)nsplit;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(decode_cached_i8_kernel, dim3((unsigned)nsplit, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a);
-    OTTER_CHECK_LAUNCH("decode_attn_cached_i8");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(decode_cached_i8_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o,
-                           (int)H, (int)nsplit);
-        OTTER_CHECK_LAUNCH("decode_attn_cached_i8 (combine)");
-    }
-    return OTTER_OK;
+    return launch_scalar<HD>(name, a, pos, split_rule<KEYS_PER_ITER>(pos + 1, N * H, cu_count()), N, stream,
+                             [](dim3 grid, hipStream_t st, const DqArgs& a) { hipLaunchKernelGGL(decode_cached_i8_kernel, grid, dim3(NT), 0, st, a); });
 }
 
 int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
@@ -301,38 +258,32 @@ int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t
                                     int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes,
                                     void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, const int32_t* pos_dev,
                                     int64_t S_max, int64_t head_dim, float scale, void* stream) {
-    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && k_scale && v_scale && o && workspace && pos_dev,
-                  "decode_attn_cached_i8_dyn: null pointer");
-    OTTER_REQUIRE((cos_table == nullptr) == (sin_table == nullptr),
-                  "decode_attn_cached_i8_dyn: cos_table and sin_table must both be given or both be NULL");
-    DQ_REQUIRE_COMMON("decode_attn_cached_i8_dyn");
-    OTTER_REQUIRE(((uintptr_t)pos_dev & 3) == 0, "decode_attn_cached_i8_dyn: pos_dev needs 4-byte alignment");
-    // any position below S_max may be read from pos_dev: the tables, the beam table and the mask must hold the capacity
-    OTTER_REQUIRE((!cos_table || table_row_stride >= HD) && (!src || src_row_stride >= S_max - 1) && (!key_valid || key_valid_row_stride >= S_max),
-                  "decode_attn_cached_i8_dyn: cos / sin tables need a row stride >= 128, src one >= S_max - 1, key_valid one >= S_max");
-    const int64_t need = OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES(N, H, S_max);
-    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_i8_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "decode_attn_cached_i8_dyn";
+    DqArgs a = {{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                 v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
+                (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
+                k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
+                src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H};
+    a.scale = scale;
+    if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, o, workspace, pos_dev})) return e;
+    if (int e = require_cos_sin_pair(name, cos_table, sin_table, "table")) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_token_and_cache_aligned(name, a)) return e;
+    if (int e = require_scales_aligned(name, a)) return e;
+    if (int e = require_cache_layout(name, &a, a, 16, S_max, HD)) return e;
+    if (int e = require_scale_head_strides(name, a, S_max)) return e;
+    if (int e = require_pos_dev_aligned(name, pos_dev)) return e;
+    if (int e = require_table_strides(name, a, table_row_stride, HD, "128", S_max)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_I8_DYN_WORKSPACE_BYTES(N, H, S_max))) return e;
 
     const int cus = cu_count();
-    const int64_t max_ranges = split_max_ranges(S_max, N * H, cus);
-
-    DqArgs a;
-    DQ_FILL_ARGS(a);
-    a.cs = cos_table; a.sn = sin_table; a.cs_rs = 0;
-    a.pos = 0; a.nsplit = 0; a.kps = 0; a.part_stride = (int)max_ranges;   // (pos, nsplit, kps: read and derived on the device)
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(decode_cached_i8_dyn_kernel, dim3((unsigned)max_ranges, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a, pos_dev, (int)S_max,
-                       cus, table_row_stride);
-    OTTER_CHECK_LAUNCH("decode_attn_cached_i8_dyn");
-    if (max_ranges > 1) {
-        hipLaunchKernelGGL(decode_cached_i8_dyn_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace,
-                           (bf16_t*)o, pos_dev, (int)N, (int)H, (int)S_max, cus, (int)max_ranges);
-        OTTER_CHECK_LAUNCH("decode_attn_cached_i8_dyn (combine)");
-    }
-    return OTTER_OK;
+    const DynStep d = {pos_dev, (int)S_max, cus, (int)split_max_ranges(S_max, N * H, cus), table_row_stride};
+    return launch_dyn(name, a, d, N, stream,
+                      [](dim3 grid, hipStream_t st, const DqArgs& a, const DynStep& d) {
+                          hipLaunchKernelGGL(decode_cached_i8_dyn_kernel, grid, dim3(NT), 0, st, a, d.pos_dev, d.S_max, d.cus, d.table_rs);
+                      },
+                      DynCombine<HD, KEYS_PER_ITER>());
 }
 
 }  // extern "C"
-
-#undef DQ_REQUIRE_COMMON
-#undef DQ_FILL_ARGS

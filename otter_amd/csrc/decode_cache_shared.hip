@@ -22,25 +22,14 @@
 // device (dyn entry), so the two entries give the same bits at every position, and two calls on the same inputs give the same bits.
 // A range, a 32-key iteration or a group's pair of keys may straddle shared_len: an iteration that lies wholly below it takes the shared
 // loader for both of its keys at once; every other iteration decides per key.
-#include "decode_split.h"
+#include "decode_cached_entry.h"
 
 namespace {
 
 constexpr int HD = 128, LANES = 16, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL;
 
-struct DsArgs {
-    const bf16_t* q; int64_t q_rs, q_hs;                  // new token: q / k / v [n, h, 128], row / head strides (elements), dim stride 1
-    const bf16_t* kn; int64_t kn_rs, kn_hs;
-    const bf16_t* vn; int64_t vn_rs, vn_hs;
-    const float *cs, *sn; int64_t cs_rs;                  // rotary row(s) of position pos, fp32 [128]; row stride 0 = shared; null = no rotary
-    bf16_t* kc; int64_t kc_rs, kc_hs;                     // cache [row, h, key, 128]: row / head strides, key stride 128
-    bf16_t* vc; int64_t vc_rs, vc_hs;
-    const int32_t* src; int64_t src_rs;                   // [N, >= pos] or null (= the row's own); columns < shared_len are not read
-    const uint8_t* kvalid; int64_t kv_rs;                 // [N, >= pos + 1] or null
-    const float* slopes;                                  // [H] or null
-    bf16_t* o;                                            // [N, H * 128]
-    float* part;                                          // [N * H * part_stride, PART] (nsplit > 1), part_stride >= nsplit
-    int N, H, pos, nsplit, kps, part_stride, shared_len;
+struct DsArgs : Bf16StepArgs {                            // (decode_cached_entry.h; columns < shared_len of `src` are not read)
+    int shared_len;
     float scale;
 };
 
@@ -200,12 +189,6 @@ __global__ __launch_bounds__(NT) void decode_shared_kernel(DsArgs a) {
     decode_shared_body<G>(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
 }
 
-// grid (H, N): one workgroup of HD lanes per (head, row), as in decode_cache.hip
-__global__ __launch_bounds__(HD) void decode_shared_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, nsplit);
-}
-
 // ---- the position in device memory (decode_split.h): grid (max_ranges, H, N / G) for the capacity ------------------------------------------
 template <int G>
 __global__ __launch_bounds__(NT) void decode_shared_dyn_kernel(DsArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus, int64_t table_rs) {
@@ -217,6 +200,8 @@ __global__ __launch_bounds__(NT) void decode_shared_dyn_kernel(DsArgs a, const i
                           a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
 }
 
+// dyn_combine_kernel of decode_cached_entry.h with NH given (it is not N * H here) and the return below shared_len: written out, the one
+// combine kernel that template does not give
 __global__ __launch_bounds__(HD) void decode_shared_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
                                                                        const int32_t* __restrict__ pos_dev, int NH, int H, int S_max, int cus,
                                                                        int max_ranges, int shared_len) {
@@ -228,65 +213,32 @@ __global__ __launch_bounds__(HD) void decode_shared_dyn_combine_kernel(const flo
     combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
 }
 
-bool mult8(int64_t a, int64_t b) { return a % 8 == 0 && b % 8 == 0; }
-
-// the instances: one per group size (OTTER_DECODE_CACHED_SHARED_MAX_GROUP of include/otter_hip.h)
-bool group_built(int64_t group) { return group >= 2 && group <= OTTER_DECODE_CACHED_SHARED_MAX_GROUP; }
-
-void launch_scalar(int group, dim3 grid, hipStream_t st, const DsArgs& a) {
+// the instances: one per group size (OTTER_DECODE_CACHED_SHARED_MAX_GROUP of include/otter_hip.h).  f(G) with G an integral constant
+template <typename F>
+void for_group(int64_t group, F&& f) {
     switch (group) {
-        case 2: hipLaunchKernelGGL(decode_shared_kernel<2>, grid, dim3(NT), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(decode_shared_kernel<3>, grid, dim3(NT), 0, st, a); break;
-        case 4: hipLaunchKernelGGL(decode_shared_kernel<4>, grid, dim3(NT), 0, st, a); break;
-        case 5: hipLaunchKernelGGL(decode_shared_kernel<5>, grid, dim3(NT), 0, st, a); break;
-        default: hipLaunchKernelGGL(decode_shared_kernel<6>, grid, dim3(NT), 0, st, a); break;
-    }
-}
-
-void launch_dyn(int group, dim3 grid, hipStream_t st, const DsArgs& a, const int32_t* pos_dev, int S_max, int cus, int64_t table_rs) {
-    switch (group) {
-        case 2: hipLaunchKernelGGL(decode_shared_dyn_kernel<2>, grid, dim3(NT), 0, st, a, pos_dev, S_max, cus, table_rs); break;
-        case 3: hipLaunchKernelGGL(decode_shared_dyn_kernel<3>, grid, dim3(NT), 0, st, a, pos_dev, S_max, cus, table_rs); break;
-        case 4: hipLaunchKernelGGL(decode_shared_dyn_kernel<4>, grid, dim3(NT), 0, st, a, pos_dev, S_max, cus, table_rs); break;
-        case 5: hipLaunchKernelGGL(decode_shared_dyn_kernel<5>, grid, dim3(NT), 0, st, a, pos_dev, S_max, cus, table_rs); break;
-        default: hipLaunchKernelGGL(decode_shared_dyn_kernel<6>, grid, dim3(NT), 0, st, a, pos_dev, S_max, cus, table_rs); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: f(std::integral_constant<int, 5>()); break;
+        default: f(std::integral_constant<int, 6>()); break;
     }
 }
 
 static_assert(OTTER_DECODE_CACHED_SHARED_MAX_GROUP == 6, "decode_cache_shared.hip: one instance per group size up to the header's limit");
 
+// the two checks of the grouping: they follow the shape's
+int require_groups(const char* name, int64_t N, int64_t group) {
+    OTTER_REQUIRE(group >= 2 && group <= OTTER_DECODE_CACHED_SHARED_MAX_GROUP, "%s: group=%ld: the kernel is built for groups of 2 to %d rows", name,
+                  (long)group, OTTER_DECODE_CACHED_SHARED_MAX_GROUP);
+    OTTER_REQUIRE(N % group == 0, "%s: N=%ld rows are not whole groups of %ld", name, (long)N, (long)group);
+    return OTTER_OK;
+}
+
 }  // namespace
 
-// the argument checks both entry points share, in the order of decode_cache.hip's (the first failing check names the error); the two checks of
-// the grouping follow the shape's
-#define DS_REQUIRE_SHAPE(NAME)                                                                                                               \
-    OTTER_REQUIRE(head_dim == HD, NAME ": head_dim %ld (128 only)", (long)head_dim);                                                        \
-    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, NAME ": bad shape N=%ld H=%ld", (long)N, (long)H);                             \
-    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, NAME ": S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT);                  \
-    OTTER_REQUIRE(group_built(group), NAME ": group=%ld: the kernel is built for groups of 2 to %d rows", (long)group,                       \
-                  OTTER_DECODE_CACHED_SHARED_MAX_GROUP);                                                                                     \
-    OTTER_REQUIRE(N % group == 0, NAME ": N=%ld rows are not whole groups of %ld", (long)N, (long)group)
-
-#define DS_REQUIRE_ALIGNED(NAME)                                                                                            \
-    OTTER_REQUIRE((((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0, \
-                  NAME ": q, k_new, v_new, k_cache, v_cache need 16-byte alignment")
-
-#define DS_REQUIRE_STRIDES(NAME)                                                                                                                    \
-    OTTER_REQUIRE(mult8(q_row_stride, q_head_stride) && mult8(k_new_row_stride, k_new_head_stride) && mult8(v_new_row_stride, v_new_head_stride) && \
-                      mult8(k_cache_row_stride, k_cache_head_stride) && mult8(v_cache_row_stride, v_cache_head_stride),                            \
-                  NAME ": q / k_new / v_new / cache strides must be multiples of 8 elements");                                                     \
-    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0,     \
-                  NAME ": a cache head stride below S_max * 128 would make the slots of two heads overlap")
-
-#define DS_FILL_ARGS(a)                                                                                                       \
-    a.q = (const bf16_t*)q; a.q_rs = q_row_stride; a.q_hs = q_head_stride;                                                    \
-    a.kn = (const bf16_t*)k_new; a.kn_rs = k_new_row_stride; a.kn_hs = k_new_head_stride;                                     \
-    a.vn = (const bf16_t*)v_new; a.vn_rs = v_new_row_stride; a.vn_hs = v_new_head_stride;                                     \
-    a.kc = (bf16_t*)k_cache; a.kc_rs = k_cache_row_stride; a.kc_hs = k_cache_head_stride;                                     \
-    a.vc = (bf16_t*)v_cache; a.vc_rs = v_cache_row_stride; a.vc_hs = v_cache_head_stride;                                     \
-    a.src = src; a.src_rs = src_row_stride; a.kvalid = key_valid; a.kv_rs = key_valid_row_stride; a.slopes = alibi_slopes;    \
-    a.o = (bf16_t*)o; a.part = (float*)workspace; a.N = (int)N; a.H = (int)H; a.scale = scale; a.shared_len = (int)shared_len
-
+// the checks of both entry points are decode_cache.hip's, in its order (the first failing check names the error), with the two checks of the
+// grouping after the shape's and the one of shared_len before the alignment's
 extern "C" {
 
 int otter_decode_attn_cached_shared(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
@@ -297,38 +249,29 @@ int otter_decode_attn_cached_shared(const void* q, int64_t q_row_stride, int64_t
                                     int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes,
                                     int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim, float scale, int64_t group,
                                     int64_t shared_len, void* stream) {
-    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && o && workspace, "decode_attn_cached_shared: null pointer");
-    OTTER_REQUIRE((cos_rows == nullptr) == (sin_rows == nullptr),
-                  "decode_attn_cached_shared: cos_rows and sin_rows must both be given or both be NULL");
-    DS_REQUIRE_SHAPE("decode_attn_cached_shared");
-    OTTER_REQUIRE(pos >= 1, "decode_attn_cached_shared: pos=%ld: a cached step continues a cache (pos >= 1)", (long)pos);
-    OTTER_REQUIRE(pos < S_max, "decode_attn_cached_shared: pos=%ld is beyond the cache capacity S_max=%ld", (long)pos, (long)S_max);
-    OTTER_REQUIRE(shared_len >= 1 && shared_len <= pos, "decode_attn_cached_shared: shared_len=%ld outside [1, pos] with pos=%ld",
-                  (long)shared_len, (long)pos);
-    DS_REQUIRE_ALIGNED("decode_attn_cached_shared");
-    DS_REQUIRE_STRIDES("decode_attn_cached_shared");
-    OTTER_REQUIRE(cos_row_stride >= 0 && (!src || src_row_stride >= pos) && (!key_valid || key_valid_row_stride >= pos + 1),
-                  "decode_attn_cached_shared: src needs a row stride >= pos, key_valid one >= pos + 1, cos / sin a non-negative one");
-    const int64_t Sk = pos + 1;
-    const int64_t need = OTTER_DECODE_CACHED_SHARED_WORKSPACE_BYTES(N, H, Sk);
-    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_shared: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "decode_attn_cached_shared";
+    DsArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                  v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
+                 (bf16_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (bf16_t*)v_cache, v_cache_row_stride, v_cache_head_stride, src,
+                 src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                (int)shared_len, scale};
+    if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, o, workspace})) return e;
+    if (int e = require_cos_sin_pair(name, cos_rows, sin_rows, "rows")) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_groups(name, N, group)) return e;
+    if (int e = require_position(name, pos, S_max)) return e;
+    OTTER_REQUIRE(shared_len >= 1 && shared_len <= pos, "%s: shared_len=%ld outside [1, pos] with pos=%ld", name, (long)shared_len, (long)pos);
+    if (int e = require_token_and_cache_aligned(name, a)) return e;
+    if (int e = require_cache_layout(name, &a, a, 8, S_max, HD)) return e;
+    if (int e = require_row_strides(name, a, &cos_row_stride, pos)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_SHARED_WORKSPACE_BYTES(N, H, pos + 1))) return e;
 
-    const Split sp = split_rule<KEYS_PER_ITER>(Sk, (N / group) * H, cu_count());
-    const int64_t nsplit = sp.nsplit;                     // <= ceil(Sk / 128): the workspace holds N * H * nsplit records
-
-    DsArgs a;
-    DS_FILL_ARGS(a);
-    a.cs = cos_rows; a.sn = sin_rows; a.cs_rs = cos_row_stride;
-    a.pos = (int)pos; a.nsplit = (int)nsplit; a.kps = sp.kps; a.part_stride = (int)nsplit;
-    hipStream_t st = (hipStream_t)stream;
-    launch_scalar((int)group, dim3((unsigned)nsplit, (unsigned)H, (unsigned)(N / group)), st, a);
-    OTTER_CHECK_LAUNCH("decode_attn_cached_shared");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(decode_shared_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o, (int)H,
-                           (int)nsplit);
-        OTTER_CHECK_LAUNCH("decode_attn_cached_shared (combine)");
-    }
-    return OTTER_OK;
+    // nsplit <= ceil((pos + 1) / 128): the workspace holds N * H * nsplit records
+    return launch_scalar<HD>(name, a, pos, split_rule<KEYS_PER_ITER>(pos + 1, (N / group) * H, cu_count()), N / group, stream,
+                             [group](dim3 grid, hipStream_t st, const DsArgs& a) {
+                                 for_group(group, [&](auto G) { hipLaunchKernelGGL(decode_shared_kernel<decltype(G)::value>, grid, dim3(NT), 0, st, a); });
+                             });
 }
 
 int otter_decode_attn_cached_shared_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
@@ -339,43 +282,39 @@ int otter_decode_attn_cached_shared_dyn(const void* q, int64_t q_row_stride, int
                                         int64_t key_valid_row_stride, const float* alibi_slopes, void* o, void* workspace,
                                         int64_t workspace_bytes, int64_t N, int64_t H, const int32_t* pos_dev, int64_t S_max, int64_t head_dim,
                                         float scale, int64_t group, int64_t shared_len, void* stream) {
-    OTTER_REQUIRE(q && k_new && v_new && k_cache && v_cache && o && workspace && pos_dev, "decode_attn_cached_shared_dyn: null pointer");
-    OTTER_REQUIRE((cos_table == nullptr) == (sin_table == nullptr),
-                  "decode_attn_cached_shared_dyn: cos_table and sin_table must both be given or both be NULL");
-    DS_REQUIRE_SHAPE("decode_attn_cached_shared_dyn");
-    OTTER_REQUIRE(shared_len >= 1 && shared_len < S_max, "decode_attn_cached_shared_dyn: shared_len=%ld outside [1, S_max) with S_max=%ld",
-                  (long)shared_len, (long)S_max);
-    DS_REQUIRE_ALIGNED("decode_attn_cached_shared_dyn");
-    OTTER_REQUIRE(((uintptr_t)pos_dev & 3) == 0, "decode_attn_cached_shared_dyn: pos_dev needs 4-byte alignment");
-    DS_REQUIRE_STRIDES("decode_attn_cached_shared_dyn");
-    // any position below S_max may be read from pos_dev: the tables, the beam table and the mask must hold the capacity
-    OTTER_REQUIRE((!cos_table || table_row_stride >= HD) && (!src || src_row_stride >= S_max - 1) && (!key_valid || key_valid_row_stride >= S_max),
-                  "decode_attn_cached_shared_dyn: cos / sin tables need a row stride >= 128, src one >= S_max - 1, key_valid one >= S_max");
-    const int64_t need = OTTER_DECODE_CACHED_SHARED_DYN_WORKSPACE_BYTES(N, H, S_max);
-    OTTER_REQUIRE(workspace_bytes >= need, "decode_attn_cached_shared_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "decode_attn_cached_shared_dyn";
+    DsArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                  v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
+                 (bf16_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (bf16_t*)v_cache, v_cache_row_stride, v_cache_head_stride, src,
+                 src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                (int)shared_len, scale};
+    if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, o, workspace, pos_dev})) return e;
+    if (int e = require_cos_sin_pair(name, cos_table, sin_table, "table")) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_groups(name, N, group)) return e;
+    OTTER_REQUIRE(shared_len >= 1 && shared_len < S_max, "%s: shared_len=%ld outside [1, S_max) with S_max=%ld", name, (long)shared_len,
+                  (long)S_max);
+    if (int e = require_token_and_cache_aligned(name, a)) return e;
+    if (int e = require_pos_dev_aligned(name, pos_dev)) return e;
+    if (int e = require_cache_layout(name, &a, a, 8, S_max, HD)) return e;
+    if (int e = require_table_strides(name, a, table_row_stride, HD, "128", S_max)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_SHARED_DYN_WORKSPACE_BYTES(N, H, S_max))) return e;
 
     const int cus = cu_count();
     const int64_t NH = (N / group) * H;
-    const int64_t max_ranges = split_max_ranges(S_max, NH, cus);   // <= ceil(S_max / 128): the workspace holds N * H * max_ranges records
-
-    DsArgs a;
-    DS_FILL_ARGS(a);
-    a.cs = cos_table; a.sn = sin_table; a.cs_rs = 0;
-    a.pos = 0; a.nsplit = 0; a.kps = 0; a.part_stride = (int)max_ranges;   // (pos, nsplit, kps: read and derived on the device)
-    hipStream_t st = (hipStream_t)stream;
-    launch_dyn((int)group, dim3((unsigned)max_ranges, (unsigned)H, (unsigned)(N / group)), st, a, pos_dev, (int)S_max, cus, table_row_stride);
-    OTTER_CHECK_LAUNCH("decode_attn_cached_shared_dyn");
-    if (max_ranges > 1) {
-        hipLaunchKernelGGL(decode_shared_dyn_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o,
-                           pos_dev, (int)NH, (int)H, (int)S_max, cus, (int)max_ranges, (int)shared_len);
-        OTTER_CHECK_LAUNCH("decode_attn_cached_shared_dyn (combine)");
-    }
-    return OTTER_OK;
+    // max_ranges <= ceil(S_max / 128): the workspace holds N * H * max_ranges records
+    const DynStep d = {pos_dev, (int)S_max, cus, (int)split_max_ranges(S_max, NH, cus), table_row_stride};
+    return launch_dyn(name, a, d, N / group, stream,
+                      [group](dim3 grid, hipStream_t st, const DsArgs& a, const DynStep& d) {
+                          for_group(group, [&](auto G) {
+                              hipLaunchKernelGGL(decode_shared_dyn_kernel<decltype(G)::value>, grid, dim3(NT), 0, st, a, d.pos_dev, d.S_max, d.cus, d.table_rs);
+                          });
+                      },
+                      [NH](dim3 grid, hipStream_t st, const DsArgs& a, const DynStep& d) {
+                          hipLaunchKernelGGL(decode_shared_dyn_combine_kernel, grid, dim3(HD), 0, st, (const float*)a.part, a.o, d.pos_dev, (int)NH, a.H,
+                                             d.S_max, d.cus, d.max_ranges, a.shared_len);
+                      });
 }
 
 }  // extern "C"
-
-#undef DS_REQUIRE_SHAPE
-#undef DS_REQUIRE_ALIGNED
-#undef DS_REQUIRE_STRIDES
-#undef DS_FILL_ARGS

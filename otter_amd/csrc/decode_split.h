@@ -1,7 +1,8 @@
-// decode_split.h -- the one statement of what the split-key (flash-decoding) cached-decode kernels share: persimmon_decode.hip,
-// persimmon_decode_cache.hip, decode_cache.hip, decode_cache_i8.hip.  Each of them keeps its Args struct, its key loop (the loaders and the
-// score terms differ: strided past + copy-out, cache through the `src` table, codes + scales; ALiBi or none, key scale or none), its
-// __global__ kernels and its entry points; the rest is here:
+// decode_split.h -- the one statement of the DEVICE half of the split-key (flash-decoding) decode kernels: persimmon_decode.hip,
+// persimmon_decode_cache.hip, decode_cache.hip, decode_cache_i8.hip, decode_cache_shared.hip.  Each of them keeps its Args struct, its key loop
+// (the loaders and the score terms differ: strided past + copy-out, cache through the `src` table, codes + scales, a shared prompt; ALiBi or
+// none, key scale or none) and its attention kernels.  The HOST half of the four cached files (argument checks, shared Args fields, combine
+// kernels, launch sequence) is decode_cached_entry.h, which includes this header; the rest is here:
 //
 //   grid (key range, head, row), NT = 256 threads.  A group of LANES lanes owns one key at a time, UNROLL keys per group in flight: score by
 //   a LANES-wide butterfly (group_sum), online softmax per group (softmax_update: running max m, sum l, o[W]) -- no score buffer, no LDS
@@ -9,7 +10,7 @@
 //   writes (m, l, o[HD]) to the workspace and a second kernel combines the ranges in range order (combine_ranges): two calls on the same
 //   inputs give the same bits.  Masked keys add nothing; a fully masked row gives o = 0.
 //
-// Every kernel of the four files compiles to the instructions it had when each file carried its own copy (tools/isa_equal.py); the forms of
+// Every kernel of these files compiles to the instructions it had when each file carried its own copy (tools/isa_equal.py); the forms of
 // softmax_update, combine_groups and DYN_POSITION_OR_RETURN below are the ones that keep it so, and the comments there say what does not.
 //
 // The includers are anonymous-namespace translation units and this header puts its contents into that namespace too: everything here has

@@ -20,7 +20,7 @@
 // CAPACITY: nothing in its launch depends on the position, so a captured graph of it can be replayed step after step.  Both derive the key
 // ranges of a position from split_rule (host and device); a workgroup of the dyn grid whose range index is not live at the current position
 // returns before it touches memory, and the combine kernel merges exactly the live ranges -- at every position the two give the same bits.
-#include "decode_split.h"
+#include "decode_cached_entry.h"
 
 namespace {
 
@@ -112,11 +112,6 @@ __global__ __launch_bounds__(NT) void persimmon_cached_kernel(PcArgs a) {
     persimmon_cached_body(a, blockIdx.x, a.pos, a.nsplit, a.kps, a.cs, a.sn);
 }
 
-__global__ __launch_bounds__(HD) void persimmon_cached_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o, int H, int nsplit) {
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, nsplit);
-}
-
 // ---- the position in device memory (decode_split.h): grid (max_ranges, H, N) for the capacity --------------------------------------------
 __global__ __launch_bounds__(NT) void persimmon_cached_dyn_kernel(PcArgs a, const int32_t* __restrict__ pos_dev, int S_max, int cus, int64_t table_rs) {
     DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)a.N * a.H, cus);
@@ -124,47 +119,15 @@ __global__ __launch_bounds__(NT) void persimmon_cached_dyn_kernel(PcArgs a, cons
     persimmon_cached_body(a, blockIdx.x, pos, sp.nsplit, sp.kps, a.cs + (int64_t)pos * table_rs, a.sn + (int64_t)pos * table_rs);   // row `pos` of the tables
 }
 
-__global__ __launch_bounds__(HD) void persimmon_cached_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
-                                                                          const int32_t* __restrict__ pos_dev, int N, int H, int S_max, int cus,
-                                                                          int max_ranges) {
-    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)N * H, cus);
-    const int nsplit = min(sp.nsplit, max_ranges);
-    if (nsplit == 1) return;                              // the one live workgroup wrote o itself
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
+int require_rot(const char* name, int64_t rot) {
+    OTTER_REQUIRE(rot > 0 && rot <= HD && rot % 16 == 0, "%s: rot=%ld must be a multiple of 16 in (0, 64]", name, (long)rot);
+    return OTTER_OK;
 }
-
-bool mult8(int64_t a, int64_t b) { return a % 8 == 0 && b % 8 == 0; }
 
 }  // namespace
 
-// the argument checks both entry points share (NAME: the entry point's name in messages).  Three macros where decode_cache_i8.hip has one:
-// here the scalar entry point checks `pos` between the shape and the alignment checks and the dyn one checks `pos_dev` between the alignment
-// and the stride checks, and the order of the checks is part of the ABI (the first failing check names the error).
-#define PC_REQUIRE_SHAPE(NAME)                                                                                                \
-    OTTER_REQUIRE(head_dim == HD, NAME ": head_dim %ld (64 only)", (long)head_dim);                                          \
-    OTTER_REQUIRE(N > 0 && H > 0 && N <= 65535 && H <= 65535, NAME ": bad shape N=%ld H=%ld", (long)N, (long)H);              \
-    OTTER_REQUIRE(rot > 0 && rot <= HD && rot % 16 == 0, NAME ": rot=%ld must be a multiple of 16 in (0, 64]", (long)rot);    \
-    OTTER_REQUIRE(S_max >= 2 && S_max <= S_MAX_LIMIT, NAME ": S_max=%ld outside [2, %ld]", (long)S_max, (long)S_MAX_LIMIT)
-
-#define PC_REQUIRE_ALIGNED(NAME) \
-    OTTER_REQUIRE((((uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0, NAME ": qkv, k_cache, v_cache need 16-byte alignment")
-
-#define PC_REQUIRE_STRIDES(NAME)                                                                                                               \
-    OTTER_REQUIRE(mult8(k_cache_row_stride, k_cache_head_stride) && mult8(v_cache_row_stride, v_cache_head_stride),                            \
-                  NAME ": cache strides must be multiples of 8 elements");                                                                    \
-    OTTER_REQUIRE(k_cache_head_stride >= S_max * HD && v_cache_head_stride >= S_max * HD && k_cache_row_stride >= 0 && v_cache_row_stride >= 0, \
-                  NAME ": a cache head stride below S_max * 64 would make the slots of two heads overlap")
-
-#define PC_FILL_ARGS(a)                                                                                  \
-    a.qkv = (const bf16_t*)qkv;                                                                          \
-    a.gq = gamma_q; a.bq = beta_q; a.gk = gamma_k; a.bk = beta_k;                                        \
-    a.kc = (bf16_t*)k_cache; a.kc_rs = k_cache_row_stride; a.kc_hs = k_cache_head_stride;                \
-    a.vc = (bf16_t*)v_cache; a.vc_rs = v_cache_row_stride; a.vc_hs = v_cache_head_stride;                \
-    a.src = src; a.src_rs = src_row_stride; a.kvalid = key_valid; a.kv_rs = key_valid_row_stride;        \
-    a.o = (bf16_t*)o; a.part = (float*)workspace;                                                        \
-    a.N = (int)N; a.H = (int)H; a.rot = (int)rot; a.eps = eps; a.scale = scale
-
+// (the order of the checks is ABI: the scalar entry point checks `pos` before the alignment checks, the dyn one `pos_dev` between the
+// alignment and the stride checks -- decode_cached_entry.h)
 extern "C" {
 
 int otter_persimmon_decode_attn_cached(const void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
@@ -173,35 +136,22 @@ int otter_persimmon_decode_attn_cached(const void* qkv, const float* gamma_q, co
                                        const int32_t* src, int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride, void* o,
                                        void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim,
                                        int64_t rot, float eps, float scale, void* stream) {
-    OTTER_REQUIRE(qkv && gamma_q && beta_q && gamma_k && beta_k && cos_row && sin_row && k_cache && v_cache && o && workspace,
-                  "persimmon_decode_attn_cached: null pointer");
-    PC_REQUIRE_SHAPE("persimmon_decode_attn_cached");
-    OTTER_REQUIRE(pos >= 1, "persimmon_decode_attn_cached: pos=%ld: a cached step continues a cache (pos >= 1)", (long)pos);
-    OTTER_REQUIRE(pos < S_max, "persimmon_decode_attn_cached: pos=%ld is beyond the cache capacity S_max=%ld", (long)pos, (long)S_max);
-    PC_REQUIRE_ALIGNED("persimmon_decode_attn_cached");
-    PC_REQUIRE_STRIDES("persimmon_decode_attn_cached");
-    OTTER_REQUIRE((!src || src_row_stride >= pos) && (!key_valid || key_valid_row_stride >= pos + 1),
-                  "persimmon_decode_attn_cached: src needs a row stride >= pos, key_valid one >= pos + 1");
-    const int64_t Sk = pos + 1;
-    const int64_t need = OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES(N, H, Sk);
-    OTTER_REQUIRE(workspace_bytes >= need, "persimmon_decode_attn_cached: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    static const char name[] = "persimmon_decode_attn_cached";
+    PcArgs a = {(const bf16_t*)qkv, gamma_q, beta_q, gamma_k, beta_k, cos_row, sin_row, (bf16_t*)k_cache, k_cache_row_stride, k_cache_head_stride,
+                (bf16_t*)v_cache, v_cache_row_stride, v_cache_head_stride, src, src_row_stride, key_valid, key_valid_row_stride, (bf16_t*)o,
+                (float*)workspace, (int)N, (int)H, 0, (int)rot, 0, 0, 0, eps, scale};
+    if (int e = require_pointers(name, {qkv, gamma_q, beta_q, gamma_k, beta_k, cos_row, sin_row, k_cache, v_cache, o, workspace})) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_rot(name, rot)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_position(name, pos, S_max)) return e;
+    if (int e = require_aligned16(name, {qkv, k_cache, v_cache}, "qkv, k_cache, v_cache")) return e;
+    if (int e = require_cache_layout(name, nullptr, a, 8, S_max, HD)) return e;
+    if (int e = require_row_strides(name, a, nullptr, pos)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_PERSIMMON_DECODE_CACHED_WORKSPACE_BYTES(N, H, pos + 1))) return e;
 
-    const Split sp = split_rule<KEYS_PER_ITER>(Sk, N * H, cu_count());
-    const int64_t nsplit = sp.nsplit;
-
-    PcArgs a;
-    PC_FILL_ARGS(a);
-    a.cs = cos_row; a.sn = sin_row;
-    a.pos = (int)pos; a.nsplit = (int)nsplit; a.kps = sp.kps; a.part_stride = (int)nsplit;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(persimmon_cached_kernel, dim3((unsigned)nsplit, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a);
-    OTTER_CHECK_LAUNCH("persimmon_decode_attn_cached");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(persimmon_cached_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace, (bf16_t*)o,
-                           (int)H, (int)nsplit);
-        OTTER_CHECK_LAUNCH("persimmon_decode_attn_cached (combine)");
-    }
-    return OTTER_OK;
+    return launch_scalar<HD>(name, a, pos, split_rule<KEYS_PER_ITER>(pos + 1, N * H, cu_count()), N, stream,
+                             [](dim3 grid, hipStream_t st, const PcArgs& a) { hipLaunchKernelGGL(persimmon_cached_kernel, grid, dim3(NT), 0, st, a); });
 }
 
 int otter_persimmon_decode_attn_cached_dyn(const void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
@@ -211,41 +161,27 @@ int otter_persimmon_decode_attn_cached_dyn(const void* qkv, const float* gamma_q
                                            int64_t key_valid_row_stride, void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H,
                                            const int32_t* pos_dev, int64_t S_max, int64_t head_dim, int64_t rot, float eps, float scale,
                                            void* stream) {
-    OTTER_REQUIRE(qkv && gamma_q && beta_q && gamma_k && beta_k && cos_table && sin_table && k_cache && v_cache && o && workspace && pos_dev,
-                  "persimmon_decode_attn_cached_dyn: null pointer");
-    PC_REQUIRE_SHAPE("persimmon_decode_attn_cached_dyn");
-    PC_REQUIRE_ALIGNED("persimmon_decode_attn_cached_dyn");
-    OTTER_REQUIRE(((uintptr_t)pos_dev & 3) == 0, "persimmon_decode_attn_cached_dyn: pos_dev needs 4-byte alignment");
-    PC_REQUIRE_STRIDES("persimmon_decode_attn_cached_dyn");
-    // any position below S_max may be read from pos_dev: the tables, the beam table and the mask must hold the capacity
-    OTTER_REQUIRE(table_row_stride >= rot && (!src || src_row_stride >= S_max - 1) && (!key_valid || key_valid_row_stride >= S_max),
-                  "persimmon_decode_attn_cached_dyn: cos / sin tables need a row stride >= rot, src one >= S_max - 1, key_valid one >= S_max");
-    const int64_t need = OTTER_PERSIMMON_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max);
-    OTTER_REQUIRE(workspace_bytes >= need, "persimmon_decode_attn_cached_dyn: workspace of %ld bytes, %ld needed", (long)workspace_bytes,
-                  (long)need);
+    static const char name[] = "persimmon_decode_attn_cached_dyn";
+    PcArgs a = {(const bf16_t*)qkv, gamma_q, beta_q, gamma_k, beta_k, cos_table, sin_table, (bf16_t*)k_cache, k_cache_row_stride, k_cache_head_stride,
+                (bf16_t*)v_cache, v_cache_row_stride, v_cache_head_stride, src, src_row_stride, key_valid, key_valid_row_stride, (bf16_t*)o,
+                (float*)workspace, (int)N, (int)H, 0, (int)rot, 0, 0, 0, eps, scale};
+    if (int e = require_pointers(name, {qkv, gamma_q, beta_q, gamma_k, beta_k, cos_table, sin_table, k_cache, v_cache, o, workspace, pos_dev})) return e;
+    if (int e = require_shape(name, head_dim, HD, N, H)) return e;
+    if (int e = require_rot(name, rot)) return e;
+    if (int e = require_capacity(name, S_max)) return e;
+    if (int e = require_aligned16(name, {qkv, k_cache, v_cache}, "qkv, k_cache, v_cache")) return e;
+    if (int e = require_pos_dev_aligned(name, pos_dev)) return e;
+    if (int e = require_cache_layout(name, nullptr, a, 8, S_max, HD)) return e;
+    if (int e = require_table_strides(name, a, table_row_stride, rot, "rot", S_max)) return e;
+    if (int e = require_workspace(name, workspace_bytes, OTTER_PERSIMMON_DECODE_CACHED_DYN_WORKSPACE_BYTES(N, H, S_max))) return e;
 
     const int cus = cu_count();
-    const int64_t max_ranges = split_max_ranges(S_max, N * H, cus);
-
-    PcArgs a;
-    PC_FILL_ARGS(a);
-    a.cs = cos_table; a.sn = sin_table;
-    a.pos = 0; a.nsplit = 0; a.kps = 0; a.part_stride = (int)max_ranges;   // (pos, nsplit, kps: read and derived on the device)
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(persimmon_cached_dyn_kernel, dim3((unsigned)max_ranges, (unsigned)H, (unsigned)N), dim3(NT), 0, st, a, pos_dev, (int)S_max,
-                       cus, table_row_stride);
-    OTTER_CHECK_LAUNCH("persimmon_decode_attn_cached_dyn");
-    if (max_ranges > 1) {
-        hipLaunchKernelGGL(persimmon_cached_dyn_combine_kernel, dim3((unsigned)H, (unsigned)N), dim3(HD), 0, st, (const float*)workspace,
-                           (bf16_t*)o, pos_dev, (int)N, (int)H, (int)S_max, cus, (int)max_ranges);
-        OTTER_CHECK_LAUNCH("persimmon_decode_attn_cached_dyn (combine)");
-    }
-    return OTTER_OK;
+    const DynStep d = {pos_dev, (int)S_max, cus, (int)split_max_ranges(S_max, N * H, cus), table_row_stride};
+    return launch_dyn(name, a, d, N, stream,
+                      [](dim3 grid, hipStream_t st, const PcArgs& a, const DynStep& d) {
+                          hipLaunchKernelGGL(persimmon_cached_dyn_kernel, grid, dim3(NT), 0, st, a, d.pos_dev, d.S_max, d.cus, d.table_rs);
+                      },
+                      DynCombine<HD, KEYS_PER_ITER>());
 }
 
 }  // extern "C"
-
-#undef PC_REQUIRE_SHAPE
-#undef PC_REQUIRE_ALIGNED
-#undef PC_REQUIRE_STRIDES
-#undef PC_FILL_ARGS
