@@ -194,9 +194,9 @@ int otter_gemm_set_persistent(int on);
  *   bit 4     timing ablation (results are WRONG: C is not written): every tile takes the masked (edge-tile) tail, which then skips its
  *             global loads and stores;  bit 6: tile-phase timeline stamps (otter_gemm_read_timeline);  bit 8: 4-wide fused tail
  *   bits 9-13 tile order of the large-grid kernel (super-tile shape, walk direction; bit 13 = one workgroup per tile)
- *   bits 14-15 (round 6) cross-tile ring of the large-grid kernel: 0 = process default (on; env OTTER_GEMM_XT), 1 = off, 2 = on
+ *   bits 14-15 (round 6) cross-tile ring of the large-grid kernel: 0 = default (on), 1 = off, 2 = on
  *   bits 16-22 + bit 23 (round 6): with bit 23 set, bits 16-22 replace the K-tile order of a tile (default 3 = rotated by the tile's N panel;
- *             0 = plain: the order the bit-for-bit comparisons against other kernels use; env OTTER_GEMM_KORDER sets the process default) */
+ *             0 = plain: the order the bit-for-bit comparisons against other kernels use) */
 int otter_gemm_set_debug(int flags);
 
 /* out[0] (op) = scale(gate) * sum(partial[0..n))   with scale = (1 - tanh(*gate)^2) when gate != NULL.

@@ -1,4 +1,4 @@
-"""Inputs with exactly known answers for the GEMM kernels (csrc/gemm.hip, gemm_t4_ktile.inc: C = epilogue(A[M, K] . B[N, K]^T)), an fp64
+"""Inputs with exactly known answers for the GEMM kernels (csrc/gemm.hip and gemm_*.hip, gemm_t4_ktile.inc: C = epilogue(A[M, K] . B[N, K]^T)), an fp64
 reference, the frames the operands and outputs are placed in, and the checkers.  Pure torch, device-agnostic: tests/test_gpu_gemm_exact.py
 feeds the checkers with ops.gemm_nt / ops.gemm, tests/test_gemm_cases_cpu.py with a plain fp64 step and with deliberately wrong ones.
 

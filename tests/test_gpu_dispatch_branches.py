@@ -17,12 +17,12 @@ Every reference is numpy / torch-CPU in fp64; for bf16 data it runs on the value
 | csrc/loss.hip | scalar tails of both vector widths, ld > V, ldd != ld | test_cross_entropy_tails_and_padded_strides |
 | csrc/optim.hip | sumsq_kernel and the AdamW kernel on p / g that are not 16-byte aligned (vec_ok false), tensors of several 8192-element chunks that end in a tail | test_fused_adamw_misaligned_views |
 | csrc/gemm.hip pick_cfg, forced | variants 1, 2 (K tail: K % 64 != 0), 3, 13, 25, 30, 26 (cross-tile form at 4 K-tiles and more, its tail-trip-only loop at K = 384, K = 128 without it, plain K order, cross-tile form off) on both sides of every tile edge, exact answers | tests/test_gpu_gemm_exact.py::test_forced_variant_at_tile_and_k_tile_edges |
-| csrc/gemm.hip epilogue4 / epilogue8 / tail_apply | STORE, accumulate, sum-of-squares partials, SCALE_RES (R fp32 / bf16), GATE_BWD (identity, squared ReLU, stashed derivative; partials), GELU (C2 = acc, C2 = GELU'), each with a gate where it takes one, full-tile and masked tails, both output dtypes | tests/test_gpu_gemm_exact.py::test_every_epilogue_form |
+| csrc/gemm_tail.h epilogue4 / epilogue8 / tail_apply | STORE, accumulate, sum-of-squares partials, SCALE_RES (R fp32 / bf16), GATE_BWD (identity, squared ReLU, stashed derivative; partials), GELU (C2 = acc, C2 = GELU'), each with a gate where it takes one, full-tile and masked tails, both output dtypes | tests/test_gpu_gemm_exact.py::test_every_epilogue_form |
 | csrc/gemm.hip gemm_impl `wide` | N, ldc, ldc2, ldr, ldaux % 8 one at a time: 4-wide against 8-wide tail | tests/test_gpu_gemm_exact.py::test_wide_tail_switch_one_leading_dimension_at_a_time |
-| csrc/gemm.hip gemm_f32_kernel | 64 x 64 x 32 tile edges, K % 32 != 0, every epilogue form | tests/test_gpu_gemm_exact.py::test_fp32_kernel_at_its_tile_edges |
+| csrc/gemm_tiled.hip gemm_f32_kernel | 64 x 64 x 32 tile edges, K % 32 != 0, every epilogue form | tests/test_gpu_gemm_exact.py::test_fp32_kernel_at_its_tile_edges |
 | otter_amd/ops.py gemm_nt `k=` | operands wider than the reduction, NaN behind column k | tests/test_gpu_gemm_exact.py::test_k_argument_reduces_over_the_first_k_columns |
-| csrc/gemm.hip persistent grids, OTTER_GRID_PER_TILE | two and more ragged tiles per workgroup under a CU budget of 8 (every persistent kernel); variant 26 with one workgroup per tile, same bits | tests/test_gpu_gemm_exact.py::test_several_tiles_per_workgroup |
-| csrc/gemm.hip gemm_bf16_t4_kernel<EPI, TA, TB, XT> by default dispatch | >= 192 tiles of 256 x 256, full and ragged; K-contiguous (cross-tile form), A / B / both K-major with padded leading dimensions, both K-major at K % 128 != 0 (rows behind K read as zeros) | tests/test_gpu_gemm_exact.py::test_default_dispatch_large_grid_and_k_major |
+| csrc/gemm.hip launch_cfg and the launch functions of csrc/gemm_*.hip: persistent grids, OTTER_GRID_PER_TILE | two and more ragged tiles per workgroup under a CU budget of 8 (every persistent kernel); variant 26 with one workgroup per tile, same bits | tests/test_gpu_gemm_exact.py::test_several_tiles_per_workgroup |
+| csrc/gemm_t4.hip gemm_bf16_t4_kernel<EPI, TA, TB, XT> by default dispatch | >= 192 tiles of 256 x 256, full and ragged; K-contiguous (cross-tile form), A / B / both K-major with padded leading dimensions, both K-major at K % 128 != 0 (rows behind K read as zeros) | tests/test_gpu_gemm_exact.py::test_default_dispatch_large_grid_and_k_major |
 """
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""The GEMM kernels (csrc/gemm.hip, gemm_t4_ktile.inc) on inputs whose answer is known exactly -- tests/_gemm_cases.py builds, places and
+"""The GEMM kernels (csrc/gemm.hip and gemm_*.hip, gemm_tail.h, gemm_t4_ktile.inc) on inputs whose answer is known exactly -- tests/_gemm_cases.py builds, places and
 checks them, tests/test_gemm_cases_cpu.py shows that the checks fail on a step that loses, doubles or shifts a k, misplaces a tile, writes
 past an edge, miscounts a partial, ignores accumulate or a leading dimension, or rounds by truncation.  Every check but the gated forms, the
 GELU value and the stashed derivative is torch.equal; those three are per element, with the constants of _gemm_cases.

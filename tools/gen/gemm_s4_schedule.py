@@ -1,4 +1,4 @@
-"""Generates the 16-slot K-tile schedule macro of gemm_bf16_s4_kernel (csrc/gemm.hip, variant 25): 128x128 tile, 4 waves of 64x64
+"""Generates the 16-slot K-tile schedule macro of gemm_bf16_s4_kernel (csrc/gemm_s4.hip, variant 25): 128x128 tile, 4 waves of 64x64
 (2x2 blocks of 32x32), BK = 64 stages in a 4-deep LDS ring.  One K-tile = 4 k-steps x 4 MFMAs.  Slot j = MFMA j, then its fillers:
 every slot requests one fragment of the NEXT k-step (k-step 0 of the next stage during the last k-step), odd slots also issue one of
 the 8 DMA pieces of stage s+3.  `python tools/gen/gemm_s4_schedule.py` prints the macro pasted between the GENERATED markers."""

@@ -1,4 +1,4 @@
-"""Generates the 128-slot K-tile schedule macros of gemm_bf16_t4_kernel (csrc/gemm.hip, variant 26): variant 18's pipeline
+"""Generates the 128-slot K-tile schedule macros of gemm_bf16_t4_kernel (csrc/gemm_t4.hip, variant 26): variant 18's pipeline
 (two 64 KB buffers, register-resident K-tile, DMA of K-tile t+2 into the buffer just freed) issued as v_mfma_f32_16x16x32_bf16.
 `python tools/gen/gemm_t4_schedule.py inc > otter_amd/csrc/gemm_t4_ktile.inc` writes the file the kernel includes.
 

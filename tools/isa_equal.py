@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Compare two device-assembly files kernel by kernel (no GPU): python tools/isa_equal.py [--rename REGEX=REPL ...] old.s new.s
 
-The files come from `hipcc <build.FLAGS> <build.EXTRA[source]> --cuda-device-only -S source.hip -o file.s` on the two trees.  A kernel is
+The files come from `hipcc <build.FLAGS> <build.EXTRA[source]> --cuda-device-only -S source.hip -o file.s` on the two trees; for kernels that
+moved between translation units (the GEMM: build.GEMM), concatenate the units' files of a tree.  A kernel is
 equal when its instruction text is equal (comments dropped, `.LBB<n>_` -> `.LBB_`: the function index in block labels shifts when kernels
 move inside the file) and its `.amdhsa_kernel` block (VGPR / AGPR / SGPR counts, LDS, scratch) is equal.  --rename rewrites OLD kernel
 names before they are matched, for kernels whose template parameter list changed.  Exit status 1 when any kernel differs or is unmatched."""
