@@ -144,6 +144,9 @@ def rmsnorm_fwd(x2d, w, eps=1e-6):
 
 
 def rmsnorm_bwd(dy, x2d, w, rstd):
+    """(dx, dw) in x's dtype / fp32.  The C function takes ONE dtype for dy, x and dx."""
+    if dy.dtype != x2d.dtype:
+        raise K.OtterHipError(f"rmsnorm_bwd: dy must have the dtype of x ({x2d.dtype}), got {dy.dtype}; rmsnorm_bwd_ex takes mixed dtypes")
     rows, D = x2d.shape
     dx = torch.empty_like(x2d)
     dw = torch.empty(D, dtype=torch.float32, device=x2d.device)

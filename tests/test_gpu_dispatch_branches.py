@@ -12,6 +12,14 @@ Every reference is numpy / torch-CPU in fp64; for bf16 data it runs on the value
 | csrc/attn_mfma.hip | a masked row whose allowed media follows several fully masked 64-key tiles | tests/test_gpu_kernels.py::test_attention_core[bf16], cases (2, 2, 40, 320, 64, 1 / 2) and (1, 4, 300, 256, 64, 1) |
 | csrc/norm.hip otter_colsum | accumulate = 1; bf16 source; D < 512 and D % 512 != 0; rows < 32; rows > 32 * 256 (the rch cap, trailing empty row chunks); a row map | test_colsum_shapes_and_accumulate |
 | csrc/norm.hip otter_layernorm_bwd | accumulate = 1 on dgamma and dbeta | test_layernorm_bwd_accumulates_weight_gradients |
+| csrc/norm.hip norm_fwd_kernel / norm_bwd_dx_kernel<NCH, RMS> | generic NCH = 1, 2, 4 (1024 < D <= 2048), 8, 16; D = 8 (one lane of 64); D = 504, 520, 1032, 2056, 4104, 8184 (lanes of the last live chunk past D, statistics divided by a D that is no power of two), exact answers | tests/test_gpu_norm_exact.py::test_forward_at_chunk_edges_every_route_and_option, ::test_backward_at_chunk_edges_every_route_and_option |
+| csrc/norm.hip dtype routes | fp32 -> bf16 on the generic kernels (D % 512 != 0; D = 4608 and 8192: NCH = 16), bf16 -> fp32, bf16 gamma / beta (ld4 and load8 on weights), otter_rmsnorm_bwd / _ex with a bf16 x (round_to in the dx and the dw kernel), add_rmsnorm_fwd without delta, rmsnorm_bwd_ex without dres, every other optional argument present and absent | the same two tests; through the wrappers: tests/test_gpu_norm_exact.py::test_ops_wrappers_every_optional_argument |
+| csrc/norm.hip norm_fwd_c_kernel / norm_bwd_dx_c_kernel<NCH, RMS> | coalesced NCH = 1, 2, 4, 8 at D = 512, 1024, 2048, 3584, 4096; bf16 weights | tests/test_gpu_norm_exact.py::test_coalescable_cases_forward_and_backward |
+| csrc/norm.hip norm_variant | OTTER_NORM_VARIANT=0 (read once per process): the generic kernels at the coalescable shapes | tests/test_gpu_norm_exact.py::test_generic_kernels_meet_the_coalesced_shapes_in_a_fresh_process |
+| csrc/norm.hip row kernels, rows < 4 | rows = 1, 2, 3, 4, 5 at D = 520 and 1024: blocks whose waves return early | tests/test_gpu_norm_exact.py::test_blocks_with_waves_that_return_early |
+| csrc/norm.hip norm_bwd_dw_partial_kernel / norm_bwd_dw_final_kernel, pick_rch | rows = 31, 32, 33, 63, 64, 65 (one row chunk becomes two, short last chunk), 127, 8191, 8192, 8193 (the cap: per = 33, empty trailing chunks over a stale workspace); accumulate, no dbeta, a dy row map, RMSNorm with a bf16 x | tests/test_gpu_norm_exact.py::test_dgamma_dbeta_at_row_chunk_edges |
+| csrc/norm.hip colsum_partial_kernel / colsum_final_kernel | the same row counts, bf16 and fp32 sources, count / one-row / one-hot forms, accumulate, a row map | tests/test_gpu_norm_exact.py::test_colsum_at_row_chunk_edges |
+| otter_amd/ops.py rmsnorm_bwd | dy of another dtype than x raises | tests/test_norm_cases_cpu.py::test_rmsnorm_bwd_rejects_a_dy_of_another_dtype, tests/test_gpu_norm_exact.py::test_ops_rmsnorm_bwd_rejects_a_dy_of_another_dtype |
 | csrc/attn.hip otter_text_time | T of exactly 64 / 128, T < 64, media at positions 63 and 64 (carry between the 64-wide scans), an all-media row | test_text_time_scan_boundaries |
 | csrc/decode.hip | Sk <= 256 boundary of the LDS floor, Sk = 1, a fully masked batch row, q as a strided slice | test_decode_attn_small_sk_and_masked_row |
 | csrc/loss.hip | scalar tails of both vector widths, ld > V, ldd != ld | test_cross_entropy_tails_and_padded_strides |
