@@ -545,6 +545,46 @@ int otter_decode_attn_cached_shared_dyn(const void* q, int64_t q_row_stride, int
                                         float scale, int64_t group, int64_t shared_len, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * otter_decode_attn_cached_shared_i8 / otter_decode_attn_cached_shared_i8_dyn -- otter_decode_attn_cached_i8 / _i8_dyn for beam search
+ * over a SHARED PROMPT: the grouping of otter_decode_attn_cached_shared over the INT8 static cache.  The arguments are those of
+ * otter_decode_attn_cached_i8 / _i8_dyn followed by `group, shared_len` (as documented for otter_decode_attn_cached_shared / _dyn:
+ * group 2 .. OTTER_DECODE_CACHED_SHARED_MAX_GROUP, N a multiple of it; 1 <= shared_len <= pos, dyn: 1 <= shared_len < S_max and a
+ * position below shared_len read from pos_dev makes the call a no-op).
+ *   src      columns < shared_len are NOT read (they count as (n / group) * group).
+ *   k_cache / v_cache / k_scale / v_scale  slots [0, shared_len) of the rows that are not leaders are NOT read.
+ *   workspace  at least OTTER_DECODE_CACHED_SHARED_I8_WORKSPACE_BYTES(N, H, pos + 1) bytes (dyn: ..._SHARED_I8_DYN_...(N, H, S_max)).
+ * The result is what otter_decode_attn_cached_i8 returns for a table whose columns [0, shared_len) hold (n / group) * group (the same
+ * arithmetic per key; the key ranges are split for N / group * H workgroups per range and a key belongs to 16 lanes, so the fixed-order
+ * sums may group differently), and the written slot [n, h, pos] of every row n -- 128 + 128 codes and two scales -- is bit-equal to that
+ * entry point's.  One workgroup serves a (key range, head, sentence): a key below shared_len is loaded and dequantised once, from the
+ * leader's row, for all `group` queries.  No workgroup reads a slot or a scale this call writes: writes are slot pos of every row, reads
+ * through src are of keys < pos, shared reads of keys < shared_len <= pos.  The fixed-order reductions (two calls on the same inputs
+ * give the same bits) and the relation of the pair (at every pos in [shared_len, S_max) the _dyn entry gives the bits of the scalar
+ * entry) are as documented for otter_decode_attn_cached / _dyn.
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_DECODE_CACHED_SHARED_I8_WORKSPACE_BYTES(N, H, Sk) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(Sk) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_shared_i8(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                       int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                       const float* cos_rows, const float* sin_rows, int64_t cos_row_stride, void* k_cache,
+                                       int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                       int64_t v_cache_head_stride, float* k_scale, int64_t k_scale_row_stride, int64_t k_scale_head_stride,
+                                       float* v_scale, int64_t v_scale_row_stride, int64_t v_scale_head_stride, const int32_t* src,
+                                       int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride, const float* alibi_slopes,
+                                       void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max,
+                                       int64_t head_dim, float scale, int64_t group, int64_t shared_len, void* stream);
+#define OTTER_DECODE_CACHED_SHARED_I8_DYN_WORKSPACE_BYTES(N, H, S_max) ((int64_t)(N) * (int64_t)(H) * (((int64_t)(S_max) + 127) / 128) * 130 * 4)
+int otter_decode_attn_cached_shared_i8_dyn(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                                           int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                                           const float* cos_table, const float* sin_table, int64_t table_row_stride, void* k_cache,
+                                           int64_t k_cache_row_stride, int64_t k_cache_head_stride, void* v_cache, int64_t v_cache_row_stride,
+                                           int64_t v_cache_head_stride, float* k_scale, int64_t k_scale_row_stride, int64_t k_scale_head_stride,
+                                           float* v_scale, int64_t v_scale_row_stride, int64_t v_scale_head_stride, const int32_t* src,
+                                           int64_t src_row_stride, const uint8_t* key_valid, int64_t key_valid_row_stride,
+                                           const float* alibi_slopes, void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H,
+                                           const int32_t* pos_dev, int64_t S_max, int64_t head_dim, float scale, int64_t group, int64_t shared_len,
+                                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * otter_xattn_decode -- the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
  * head_dim 64: N rows (batch x beams) of ONE query each attend over the projected media of their sentence.
  *   q        bf16 [N, H * 64] with a row stride (elements, a multiple of 8, >= H * 64), 16-byte aligned.

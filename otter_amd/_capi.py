@@ -153,6 +153,12 @@ SIGNATURES = {
     "otter_decode_attn_cached_shared_dyn": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
                                                    _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _f32, _i64, _i64,
                                                    _vp]),
+    "otter_decode_attn_cached_shared_i8": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64,
+                                                  _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                                  _i64, _f32, _i64, _i64, _vp]),
+    "otter_decode_attn_cached_shared_i8_dyn": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
+                                                      _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
+                                                      _vp, _i64, _i64, _f32, _i64, _i64, _vp]),
     "otter_xattn_decode": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _vp]),
     "otter_gemv_w8": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
     "otter_gemm_w8_rows": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),

@@ -68,12 +68,16 @@ LEADER, row (n // group) * group):
                 cached step (and before `enable_replay`, which must find it: its address is fixed before capture).
 
 `reorder` is unchanged: beam search never moves a row to another sentence (the precondition; checked where the index is a CPU tensor), so the
-prefix columns stay on the leader whatever the ancestry.  `attend_reference`, `to_legacy` and the int8 kernels read through the table as they
-are.  In bf16 at head_dim 128 `attend` takes csrc/decode_cache_shared.hip (`ops.decode_attn_cached_shared`, `_dyn` in replay mode) for the
+prefix columns stay on the leader whatever the ancestry.  `attend_reference`, `to_legacy` and the ungrouped kernels read through the table as
+they are.  In bf16 at head_dim 128 `attend` takes csrc/decode_cache_shared.hip (`ops.decode_attn_cached_shared`, `_dyn` in replay mode) for the
 group sizes it is built for, from SHARED_KERNEL_MIN_KEYS = 1 536 shared keys per head on (sentences x shared_len; below that the step is
 latency-bound and the table path is as fast or faster): one workgroup carries the `group` queries of a sentence and loads each shared key
 once.  OTTER_SHARED_PREFIX=0 keeps the table path (the A/B lever, like OTTER_HIP_BEAM) and =1 takes the kernel below the threshold too; other
-group sizes and the int8 cache stay on the table path, so the int8 form gets the saving of the prompt pass only.  The layout and the
+group sizes stay on the table path.  The int8 cache has its own grouped kernel, csrc/decode_cache_shared_i8.hip
+(`ops.decode_attn_cached_shared_i8`, `_dyn` in replay mode; `uses_shared_i8_kernel`): a shared key's codes and scales are loaded and
+dequantised once for the group, from SHARED_I8_KERNEL_MIN_KEYS shared keys per head on.  Its lever is OTTER_SHARED_PREFIX_I8 ("0": the table
+path through csrc/decode_cache_i8.hip; "1": the kernel below the threshold too); OTTER_SHARED_PREFIX=0 switches it off as well, and
+OTTER_SHARED_PREFIX=1 does not force it.  The layout and the
 allocation stay as they are: the non-leader rows' slots [0, shared_len) are allocated and never touched, so sharing saves prompt-pass work
 and key / value traffic, not cache memory.
 """
@@ -87,6 +91,9 @@ import torch
 
 # a shared prompt: the grouped kernel from this many shared keys per head on (sentences x shared_len); measured, DESIGN.md 4.19
 SHARED_KERNEL_MIN_KEYS = 1536
+# the same for the int8 cache's grouped kernel (csrc/decode_cache_shared_i8.hip): the smallest measured count from which no measured point,
+# kernel alone or whole generate() call, was more than 3 % slower than the table path (profiles/r20_shared_prefix_i8_ab.txt)
+SHARED_I8_KERNEL_MIN_KEYS = 16384
 
 
 def rotate_half(x: torch.Tensor) -> torch.Tensor:
@@ -367,6 +374,21 @@ class StaticKVCache:
 
         return self.group in ops.DECODE_CACHED_SHARED_GROUPS and self.uses_kernel(q, n_kv)
 
+    def uses_shared_i8_kernel(self, q: torch.Tensor, n_kv: int) -> bool:
+        """The step runs on csrc/decode_cache_shared_i8.hip: an int8 cache with a shared prompt in a group size that kernel is built for,
+        where `uses_kernel` holds, OTTER_SHARED_PREFIX != "0" (that lever switches every grouped kernel off) and OTTER_SHARED_PREFIX_I8 != "0"
+        (this kernel's own A/B lever: "0" keeps csrc/decode_cache_i8.hip, through the table).  Unless OTTER_SHARED_PREFIX_I8 is "1" the kernel
+        is taken only from SHARED_I8_KERNEL_MIN_KEYS shared keys per head on (sentences x shared_len).  OTTER_SHARED_PREFIX=1 does not force
+        it.  All of this is fixed for a whole generate call, so a captured step keeps its kernel."""
+        lever = os.environ.get("OTTER_SHARED_PREFIX_I8", "")
+        if not self.int8 or self.group < 2 or self.shared_len < 1 or lever == "0" or os.environ.get("OTTER_SHARED_PREFIX", "") == "0":
+            return False
+        if lever != "1" and (self.rows // self.group) * self.shared_len < SHARED_I8_KERNEL_MIN_KEYS:
+            return False
+        from . import ops
+
+        return self.group in ops.DECODE_CACHED_SHARED_I8_GROUPS and self.uses_kernel(q, n_kv)
+
     def attend(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
         """One cached step of `layer` at position `length` (which the caller advances once per forward, after the last layer):
         q [N,H,d], k_new / v_new [N,H_kv,d] views of the projection output; cos / sin fp32 [d] rows of that position or None;
@@ -379,6 +401,10 @@ class StaticKVCache:
             if self.uses_kernel(q, k_new.shape[1]):
                 from . import ops
 
+                if self.uses_shared_i8_kernel(q, k_new.shape[1]):
+                    return ops.decode_attn_cached_shared_i8_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer],
+                                                                self.v_scale[layer], self.pos_dev, scale, self.group, self.shared_len,
+                                                                cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid, slopes=slopes)
                 if self.int8:
                     return ops.decode_attn_cached_i8_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
                                                          self.pos_dev, scale, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
@@ -394,6 +420,10 @@ class StaticKVCache:
         if self.uses_kernel(q, k_new.shape[1]):
             from . import ops
 
+            if self.uses_shared_i8_kernel(q, k_new.shape[1]):
+                return ops.decode_attn_cached_shared_i8(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
+                                                        self.length, scale, self.group, self.shared_len, cos=cos, sin=sin, src=self.src,
+                                                        key_valid=key_valid, slopes=slopes)
             if self.int8:
                 return ops.decode_attn_cached_i8(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
                                                  self.length, scale, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)

@@ -868,6 +868,44 @@ def decode_attn_cached_shared_dyn(q, k_new, v_new, k_cache, v_cache, pos_dev, sc
     return o
 
 
+# csrc/decode_cache_shared_i8.hip: every group size of DECODE_CACHED_SHARED_GROUPS has an instance (none was left on the table path)
+DECODE_CACHED_SHARED_I8_GROUPS = DECODE_CACHED_SHARED_GROUPS
+
+decode_attn_cached_shared_i8_workspace_bytes = decode_attn_cached_shared_i8_dyn_workspace_bytes = decode_attn_cached_workspace_bytes
+
+
+def decode_attn_cached_shared_i8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos, scale, group, shared_len, cos=None, sin=None, src=None,
+                                 key_valid=None, slopes=None):
+    """decode_attn_cached_i8 for beam search over a shared prompt (otter_decode_attn_cached_shared_i8): the grouping of
+    decode_attn_cached_shared over the int8 cache.  Keys [0, shared_len) of every beam are read from the sentence's first row -- codes and
+    scales, once for the whole group, dequantised once -- what decode_attn_cached_i8 returns for a table whose columns [0, shared_len) hold
+    (n // group) * group; columns < shared_len of `src` and the other rows' codes and scales [0, shared_len) are not read.
+    group in DECODE_CACHED_SHARED_I8_GROUPS, N % group == 0, 1 <= shared_len <= pos.  Everything else as decode_attn_cached_i8.
+    Returns o [N,H*128] bf16."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cos, sin, src, key_valid, slopes)
+    name = "decode_attn_cached_shared_i8"
+    args, o = _decode_cached_args(name, False, q, k_new, v_new, k_cache, v_cache, (k_scale, v_scale), pos, scale, cos, sin, src, key_valid, slopes,
+                                  None)
+    grouping = _check_shared(name, False, q.shape[0], group, shared_len, int(pos), k_cache.shape[2])
+    K.check(K.lib().otter_decode_attn_cached_shared_i8(*args, *grouping, K.stream()), name)
+    return o
+
+
+def decode_attn_cached_shared_i8_dyn(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos_dev, scale, group, shared_len, cos_table=None,
+                                     sin_table=None, src=None, key_valid=None, slopes=None, out=None):
+    """decode_attn_cached_shared_i8 with the position in device memory (otter_decode_attn_cached_shared_i8_dyn): every argument but `group`
+    and `shared_len` as decode_attn_cached_i8_dyn; 1 <= shared_len < S_max, a host scalar that stays the same over a generate() call (a
+    position below it, like one outside [1, S_max), makes the call a no-op).  Returns o [N,H*128] bf16 (`out`: a contiguous bf16 [N,H*128]
+    tensor to write instead)."""
+    K.require_cuda(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, pos_dev, cos_table, sin_table, src, key_valid, slopes, out)
+    name = "decode_attn_cached_shared_i8_dyn"
+    args, o = _decode_cached_args(name, True, q, k_new, v_new, k_cache, v_cache, (k_scale, v_scale), pos_dev, scale, cos_table, sin_table, src,
+                                  key_valid, slopes, out)
+    grouping = _check_shared(name, True, q.shape[0], group, shared_len, None, k_cache.shape[2])
+    K.check(K.lib().otter_decode_attn_cached_shared_i8_dyn(*args, *grouping, K.stream()), name)
+    return o
+
+
 XATTN_DECODE_MAX_KEYS = 65536         # include/otter_hip.h: M = T_img * n_per_media <= 65536
 
 

@@ -18,8 +18,18 @@ Parts (each a child process of this tool under its own `timeout`; the tool stops
 Beside every measured ratio the bytes ratio (P / nb + own) / (P + own) of the keys and values a step reads (own: the mean over the call).
 Condition, per point: the share_prompt path <= 1.03 x the parent path (3 %: tools/regress.sh's margin); a point that misses prints MISS.
 
+--kv-dtype int8 (the default, bf16, leaves every line above as it is): the int8 static cache and csrc/decode_cache_shared_i8.hip.
+  kernel    the contenders are ops.decode_attn_cached_shared_i8 (grouped), ops.decode_attn_cached_i8 through the same table (table: what
+            OTTER_SHARED_PREFIX_I8=0 and the parent commit run for a share_prompt call) and ops.decode_attn_cached_i8 on private copies
+            (private: what the parent commit runs for an unshared call).  The points above plus rows 3 x {1024, 1536} and rows 24 x 128 shared
+            keys, around the count from which `attend` takes the grouped kernel.  A cached vector is 132 bytes (128 codes + one fp32 scale):
+            the distinct bytes are (sentences x P + rows x 64) x 32 x 264 for grouped and table, rows x (P + 64) x 32 x 264 for private.
+            Condition: grouped <= 1.03 x table and <= 1.03 x private.
+  generate  the same call plus kv_cache_dtype="int8", share_prompt=True on both sides: OTTER_SHARED_PREFIX_I8=0 (the parent commit's
+            behaviour: the table path) against the variable unset, alternated in one process.
+
   python tools/shared_prefix_bench.py [--parts kernel generate] [--sentences 8 1] [--prompts 512 1536] [--rounds 3] [--new 128] [--layers 32]
-                                      [--append] [--out profiles/r19_shared_prefix_ab.txt]"""
+                                      [--kv-dtype bf16|int8] [--append] [--out profiles/r19_shared_prefix_ab.txt]"""
 from __future__ import annotations
 
 import argparse
@@ -42,6 +52,9 @@ NB, OWN = 3, 64
 PART_SECONDS = {"kernel": 300, "generate": 1080}
 CALLS, REPS = 64, 5
 CONTENDERS = ("grouped", "table", "private")
+# --kv-dtype int8: (rows, shared keys) of the kernel part -- the bf16 part's points, then those around the dispatch threshold
+I8_POINTS = [(rows, P) for rows in (24, 3) for P in (512, 2048, 8192)] + [(3, 1024), (3, 1536), (24, 128)]
+I8_LEVER = "OTTER_SHARED_PREFIX_I8"
 
 
 # ---- part: kernel ---------------------------------------------------------------------------------------------------------------------
@@ -112,12 +125,90 @@ def kernel_part(a, say):
     return result
 
 
+def kernel_part_i8(a, say):
+    """The kernel part over the int8 cache (module docstring)."""
+    from otter_amd import ops
+
+    dev, H = "cuda:0", 32
+    g = torch.Generator(device=dev).manual_seed(0)
+    slopes = (2.0 ** -(8.0 * torch.arange(1, H + 1, device=dev, dtype=torch.float32) / H)).contiguous()
+    result, misses = {}, 0
+    for rows, P in I8_POINTS:
+        pos, S_max = P + OWN, P + OWN + 8
+        per_layer = rows * H * S_max * 132 * 2
+        layers = min(64, max(2, -(-(1 << 30) // per_layer)))
+        qkv = torch.randn(rows, 3, H, 128, device=dev, generator=g).bfloat16()
+        q, k, v = qkv[:, 0], qkv[:, 1], qkv[:, 2]
+        kb = torch.randint(-127, 128, (layers, rows, H, S_max, 128), device=dev, generator=g, dtype=torch.int8)
+        vb = torch.randint(-127, 128, (layers, rows, H, S_max, 128), device=dev, generator=g, dtype=torch.int8)
+        ksb = (0.5 + torch.rand(layers, rows, H, S_max, device=dev, generator=g)) * (3.0 / 127)
+        vsb = (0.5 + torch.rand(layers, rows, H, S_max, device=dev, generator=g)) * (3.0 / 127)
+        n = torch.arange(rows, dtype=torch.int32, device=dev)
+        own = (n // NB * NB + (n % NB + 1) % NB)[:, None].repeat(1, S_max - 1)        # the own part behind a sibling, as after a reorder
+        shared = own.clone()
+        shared[:, :P] = (n // NB * NB)[:, None]
+        private = own.clone()
+        private[:, :P] = n[:, None]
+
+        def call(c, i):
+            L = i % layers
+            if c == "grouped":
+                return ops.decode_attn_cached_shared_i8(q, k, v, kb[L], vb[L], ksb[L], vsb[L], pos, 0.0884, NB, P, src=shared, slopes=slopes)
+            return ops.decode_attn_cached_i8(q, k, v, kb[L], vb[L], ksb[L], vsb[L], pos, 0.0884, src=shared if c == "table" else private,
+                                             slopes=slopes)
+
+        us = {c: [] for c in CONTENDERS}
+        for c in CONTENDERS:
+            for i in range(8):
+                call(c, i)
+        for _ in range(REPS):
+            for c in CONTENDERS:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for i in range(CALLS):
+                    call(c, i)
+                e1.record()
+                torch.cuda.synchronize()
+                us[c].append(e0.elapsed_time(e1) * 1e3 / CALLS)
+        med = {c: sorted(us[c])[REPS // 2] for c in CONTENDERS}
+        spread = {c: (max(us[c]) - min(us[c])) / med[c] for c in CONTENDERS}
+        distinct = (rows // NB * P + rows * OWN) * H * 264
+        nbytes = {"grouped": distinct, "table": distinct, "private": rows * pos * H * 264}
+        tbps = {c: nbytes[c] / (med[c] * 1e-6) / 1e12 for c in CONTENDERS}
+        over_private, over_table, bytes_ratio = med["grouped"] / med["private"], med["grouped"] / med["table"], (P / NB + OWN) / (P + OWN)
+        tag = "kernel int8 rows=%d shared=%d own=%d" % (rows, P, OWN)
+        say("%s (sentences x shared = %d; %d caches in turn): grouped %.1f us (%.1f MB, %.2f TB/s) | table %.1f us (%.2f TB/s) | private %.1f us "
+            "(%.1f MB, %.2f TB/s) | grouped = x%.3f of table, x%.3f of private; table = x%.3f of private (bytes ratio %.3f; spread %.1f / %.1f / "
+            "%.1f %%)" % (tag, rows // NB * P, layers, med["grouped"], distinct / 1e6, tbps["grouped"], med["table"], tbps["table"], med["private"],
+                          nbytes["private"] / 1e6, tbps["private"], over_table, over_private, med["table"] / med["private"], bytes_ratio,
+                          spread["grouped"] * 100, spread["table"] * 100, spread["private"] * 100))
+        if max(over_private, over_table) > THRESHOLD:
+            misses += 1
+            say("MISS: %s: the grouped kernel is more than %.0f %% slower than the existing int8 kernel %s" % (
+                tag, (THRESHOLD - 1) * 100, "through the table" if over_table > THRESHOLD else "on private copies"))
+        result[tag] = {"us": med, "all_us": us, "bytes": nbytes, "tbps": tbps, "grouped_over_private": over_private, "grouped_over_table": over_table,
+                       "bytes_ratio": bytes_ratio, "sentences_x_shared": rows // NB * P}
+        del kb, vb, ksb, vsb
+        gc.collect()
+        torch.cuda.empty_cache()
+    say("part kernel (int8): conditions missed: %d of %d" % (misses, len(result)))
+    return result
+
+
 # ---- part: generate -------------------------------------------------------------------------------------------------------------------
 
 @torch.no_grad()
 def timed_generate(model, vx, ids, new, kw):
-    """(seconds, capture seconds, tokens) of one generate call."""
+    """(seconds, capture seconds, tokens) of one generate call.  An "env" entry of `kw` is not a keyword: {variable: value or None (unset)}
+    for the duration of the call."""
     from otter_amd.graph_decode import GraphDecodeStep
+
+    kw = dict(kw)
+    env = kw.pop("env", {})
+    saved = {name: os.environ.get(name) for name in env}
+    for name, value in env.items():
+        os.environ.pop(name, None) if value is None else os.environ.__setitem__(name, value)
 
     captured, release = [0.0], GraphDecodeStep.release
 
@@ -136,6 +227,8 @@ def timed_generate(model, vx, ids, new, kw):
         return time.perf_counter() - t0, captured[0], toks
     finally:
         GraphDecodeStep.release = release
+        for name, value in saved.items():
+            os.environ.pop(name, None) if value is None else os.environ.__setitem__(name, value)
 
 
 def generate_part(a, say):
@@ -149,6 +242,10 @@ def generate_part(a, say):
         NB, torch.cuda.memory_allocated() / 1e9))
     base = dict(cache_implementation="static", cross_attention_cache=True, graph_decode=True, num_beams=NB, no_repeat_ngram_size=3)
     kw = {"parent": base, "shared": dict(base, share_prompt=True)}
+    if a.kv_dtype == "int8":        # share_prompt on both sides; the parent commit's behaviour is the table path
+        base = dict(base, kv_cache_dtype="int8", share_prompt=True)
+        kw = {"parent": dict(base, env={I8_LEVER: "0"}), "shared": dict(base, env={I8_LEVER: None})}
+        say("int8 KV cache, share_prompt=True on both sides: parent = %s=0 (the table path), shared = %s unset" % (I8_LEVER, I8_LEVER))
     med = lambda xs: sorted(xs)[len(xs) // 2]
     result, misses = {}, 0
     for B in a.sentences:
@@ -195,7 +292,7 @@ def generate_part(a, say):
 
 def run_child(a, part):
     cmd = ["timeout", "-k", "10", str(PART_SECONDS[part]), sys.executable, os.path.abspath(__file__), "--child", part, "--rounds", str(a.rounds),
-           "--new", str(a.new), "--layers", str(a.layers), "--sentences"] + [str(r) for r in a.sentences] + ["--prompts"] + [str(p) for p in a.prompts]
+           "--new", str(a.new), "--layers", str(a.layers), "--kv-dtype", a.kv_dtype, "--sentences"] + [str(r) for r in a.sentences] + ["--prompts"] + [str(p) for p in a.prompts]
     # its own process group: on a time limit the whole group goes, here and by `timeout`
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, start_new_session=True, text=True)
     out = []
@@ -218,6 +315,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--kv-dtype", choices=["bf16", "int8"], default="bf16")
     ap.add_argument("--child", choices=list(PART_SECONDS), default=None)
     ap.add_argument("--append", action="store_true")
     ap.add_argument("--out", default=None)
@@ -228,11 +326,12 @@ def main():
         say = lambda s: print(s, flush=True)
         dev = torch.cuda.get_device_properties(0)
         say("device: %s, %d CUs; torch %s" % (dev.name, dev.multi_processor_count, torch.__version__))
-        result = kernel_part(a, say) if a.child == "kernel" else generate_part(a, say)
+        kernel = kernel_part_i8 if a.kv_dtype == "int8" else kernel_part
+        result = kernel(a, say) if a.child == "kernel" else generate_part(a, say)
         say(json.dumps(result))
         return
     lines = ["shared_prefix_bench: parts %s; sentences %s; prompts %s; %d rounds; %d new tokens; %d decoder layers" % (
-        " ".join(a.parts), a.sentences, a.prompts, a.rounds, a.new, a.layers)]
+        " ".join(a.parts), a.sentences, a.prompts, a.rounds, a.new, a.layers) + ("; int8 KV cache" if a.kv_dtype == "int8" else "")]
     status = 0
     for part in a.parts:
         rc, out = run_child(a, part)
