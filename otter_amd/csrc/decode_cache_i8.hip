@@ -6,9 +6,8 @@
 // in-place update rests on: no workgroup reads a slot (codes or scale) that this launch writes.  Scales are per token, so an append never
 // rewrites the scale of an earlier position.
 //
-// THE FORMAT (kv_cache.py states it once): for the vector x[128] the bf16 cache would hold (k after rotary, rounded once to bf16; v as given),
-// read as fp32:   amax = max |x[i]|;  scale = amax / 127 (1 when amax == 0);  code = clamp(rint(x[i] / scale), -127, 127);  value = code * scale.
-// Plain `/` and rintf (round-half-even): IEEE-exact ops, the same codes and scales as torch computes.  No reciprocal.
+// THE FORMAT (amax, scale, code, value) is kv_i8_scale / kv_i8_code of csrc/decode_split.h, under its comment there; kv_cache.py states it
+// for the project.  DqArgs' fields, the checks of the scales and the launch code are csrc/decode_cached_entry.h's.
 //
 // The new token is attended in its DEQUANTISED form (codes and scale from LDS), so a step returns what "append, then attend over the cache"
 // returns.
@@ -23,29 +22,9 @@ namespace {
 
 constexpr int HD = 128, LANES = 8, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL, DPL = HD / LANES;
 
-struct DqArgs : NewTokenArgs {                            // (decode_cached_entry.h: q / k / v of the new token, the rotary rows)
-    int8_t* kc; int64_t kc_rs, kc_hs;                     // codes [row, h, key, 128]: row / head strides, key stride 128
-    int8_t* vc; int64_t vc_rs, vc_hs;
-    float* ks; int64_t ks_rs, ks_hs;                      // scales [row, h, key]: row / head strides, key stride 1
-    float* vs; int64_t vs_rs, vs_hs;
-    const int32_t* src; int64_t src_rs;                   // [N, >= pos] or null (= the row's own)
-    const uint8_t* kvalid; int64_t kv_rs;                 // [N, >= pos + 1] or null
-    const float* slopes;                                  // [H] or null
-    bf16_t* o;                                            // [N, H * 128]
-    float* part;                                          // [N * H * part_stride, PART] (nsplit > 1), part_stride >= nsplit
-    int N, H, pos, nsplit, kps, part_stride;
+struct DqArgs : I8StepArgs {                              // (decode_cached_entry.h: the new token, codes and scales, the tables, o, the ranges)
     float scale;
 };
-
-// 16 int8 codes -> 16 floats (exact)
-__device__ __forceinline__ void unpack16(const uint4& r, float (&v)[DPL]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) v[4 * i + b] = (float)(int)(int8_t)(w[i] >> (8 * b));
-    }
-}
 
 // one workgroup's share of a step: range `split` of row blockIdx.z, head blockIdx.y
 __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int split, const int pos, const int nsplit, const int kps,
@@ -73,8 +52,8 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
         if ((tid & (OTTER_WAVE - 1)) == 0) wave_amax[tid / OTTER_WAVE] = wm;
         __syncthreads();
         const float amax = fmaxf(wave_amax[tid < HD ? 0 : 2], wave_amax[tid < HD ? 1 : 3]);
-        const float sc = amax == 0.f ? 1.f : amax / 127.f;
-        const float c = fminf(fmaxf(rintf(x / sc), -127.f), 127.f);
+        const float sc = kv_i8_scale(amax);
+        const float c = kv_i8_code(x, sc);
         code_new[which][d] = (int8_t)(int)c;
         if (d == 0) scale_new[which] = sc;
     }
@@ -87,7 +66,7 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
     if (pos >= j0 && pos < j1) {
         if (tid < 2 * LANES) {
             int8_t* dst = (tid < LANES ? a.kc + n * a.kc_rs + h * a.kc_hs : a.vc + n * a.vc_rs + h * a.vc_hs) + (int64_t)pos * HD + DPL * l8;
-            *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&code_new[tid < LANES ? 0 : 1][DPL * l8]);
+            *reinterpret_cast<Codes<DPL>*>(dst) = *reinterpret_cast<const Codes<DPL>*>(&code_new[tid < LANES ? 0 : 1][DPL * l8]);
         } else if (tid < 2 * LANES + 2) {
             const int w = tid - 2 * LANES;
             float* dst = w == 0 ? a.ks + n * a.ks_rs + h * a.ks_hs : a.vs + n * a.vs_rs + h * a.vs_hs;
@@ -110,7 +89,7 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
 #pragma unroll
     for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
     for (int jb = j0; jb < j1; jb += KEYS_PER_ITER) {
-        uint4 kr[UNROLL], vr[UNROLL];
+        Codes<DPL> kr[UNROLL], vr[UNROLL];
         float ksc[UNROLL], vsc[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
@@ -118,18 +97,18 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
             if (j < j1 && j < pos) {
                 // a table entry outside [0, N) is clamped: it can make the result wrong, never an access outside the cache
                 const int64_t row = src ? (int64_t)min(max(src[j], 0), a.N - 1) : (int64_t)n;
-                kr[u] = *reinterpret_cast<const uint4*>(kb + row * a.kc_rs + (int64_t)j * HD);
-                vr[u] = *reinterpret_cast<const uint4*>(vb + row * a.vc_rs + (int64_t)j * HD);
+                kr[u] = *reinterpret_cast<const Codes<DPL>*>(kb + row * a.kc_rs + (int64_t)j * HD);
+                vr[u] = *reinterpret_cast<const Codes<DPL>*>(vb + row * a.vc_rs + (int64_t)j * HD);
                 ksc[u] = ksb[row * a.ks_rs + j];
                 vsc[u] = vsb[row * a.vs_rs + j];
             } else if (j < j1) {                          // j == pos: the new token, as the cache now holds it
-                kr[u] = *reinterpret_cast<const uint4*>(&code_new[0][DPL * l8]);
-                vr[u] = *reinterpret_cast<const uint4*>(&code_new[1][DPL * l8]);
+                kr[u] = *reinterpret_cast<const Codes<DPL>*>(&code_new[0][DPL * l8]);
+                vr[u] = *reinterpret_cast<const Codes<DPL>*>(&code_new[1][DPL * l8]);
                 ksc[u] = scale_new[0];
                 vsc[u] = scale_new[1];
             } else {
-                kr[u] = make_uint4(0, 0, 0, 0);
-                vr[u] = make_uint4(0, 0, 0, 0);
+                kr[u] = Codes<DPL>{};
+                vr[u] = Codes<DPL>{};
                 ksc[u] = 0.f;
                 vsc[u] = 0.f;
             }
@@ -139,15 +118,15 @@ __device__ __forceinline__ void decode_cached_i8_body(const DqArgs& a, const int
             const int j = jb + u * GROUPS + g;
             const bool live = j < j1;
             float k[DPL], v[DPL];
-            unpack16(kr[u], k);
-            unpack16(vr[u], v);
+            unpack_codes(kr[u], k);
+            unpack_codes(vr[u], v);
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < DPL; ++i) s = fmaf(q[i], k[i], s);
             s = group_sum<LANES>(s);                      // (all lanes: the shuffles stay convergent)
             s = fmaf(s, ksc[u], slope * (float)(j - pos));
             if (!live || (kv && kv[j] == 0)) s = -INFINITY;
-            const float mn = fmaxf(m, s);                 // (softmax_update of decode_split.h, with the value scale; see there)
+            const float mn = fmaxf(m, s);                 // (softmax_update_scaled of decode_split.h, written out; see there)
             if (mn != -INFINITY) {
                 const float alpha = __expf(m - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
                 const float pv = p * vsc[u];
@@ -200,18 +179,6 @@ __global__ __launch_bounds__(NT) void decode_cached_i8_dyn_kernel(DqArgs a, cons
                           a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
 }
 
-// the two checks of the scales: their alignment follows the codes', their head strides the codes'
-int require_scales_aligned(const char* name, const DqArgs& a) {
-    OTTER_REQUIRE((((uintptr_t)a.ks | (uintptr_t)a.vs) & 3) == 0, "%s: k_scale, v_scale need 4-byte alignment", name);
-    return OTTER_OK;
-}
-
-int require_scale_head_strides(const char* name, const DqArgs& a, int64_t S_max) {
-    OTTER_REQUIRE(a.ks_hs >= S_max && a.vs_hs >= S_max && a.ks_rs >= 0 && a.vs_rs >= 0,
-                  "%s: a scale head stride below S_max would make the scales of two heads overlap", name);
-    return OTTER_OK;
-}
-
 }  // namespace
 
 // (here the position's check, `pos` or `pos_dev`, follows every check of the layout: the order of this file's entry points since they exist)
@@ -227,12 +194,12 @@ int otter_decode_attn_cached_i8(const void* q, int64_t q_row_stride, int64_t q_h
                                 int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max, int64_t head_dim, float scale,
                                 void* stream) {
     static const char name[] = "decode_attn_cached_i8";
-    DqArgs a = {{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
-                 v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
-                (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
-                k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
-                src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H};
-    a.scale = scale;
+    DqArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                  v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
+                 (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
+                 k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
+                 src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                scale};
     if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, o, workspace})) return e;
     if (int e = require_cos_sin_pair(name, cos_rows, sin_rows, "rows")) return e;
     if (int e = require_shape(name, head_dim, HD, N, H)) return e;
@@ -259,12 +226,12 @@ int otter_decode_attn_cached_i8_dyn(const void* q, int64_t q_row_stride, int64_t
                                     void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, const int32_t* pos_dev,
                                     int64_t S_max, int64_t head_dim, float scale, void* stream) {
     static const char name[] = "decode_attn_cached_i8_dyn";
-    DqArgs a = {{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
-                 v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
-                (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
-                k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
-                src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H};
-    a.scale = scale;
+    DqArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                  v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
+                 (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
+                 k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
+                 src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                scale};
     if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, o, workspace, pos_dev})) return e;
     if (int e = require_cos_sin_pair(name, cos_table, sin_table, "table")) return e;
     if (int e = require_shape(name, head_dim, HD, N, H)) return e;

@@ -22,6 +22,9 @@
 // device (dyn entry), so the two entries give the same bits at every position, and two calls on the same inputs give the same bits.
 // A range, a 32-key iteration or a group's pair of keys may straddle shared_len: an iteration that lies wholly below it takes the shared
 // loader for both of its keys at once; every other iteration decides per key.
+//
+// What this file has in common with its int8 form, decode_cache_shared_i8.hip, is csrc/decode_cached_entry.h's: the checks of the grouping and
+// of shared_len, the switch over the group size (for_group) and the dyn combine kernel (shared_dyn_combine_kernel).  The two key loops are not.
 #include "decode_cached_entry.h"
 
 namespace {
@@ -200,41 +203,6 @@ __global__ __launch_bounds__(NT) void decode_shared_dyn_kernel(DsArgs a, const i
                           a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
 }
 
-// dyn_combine_kernel of decode_cached_entry.h with NH given (it is not N * H here) and the return below shared_len: written out, the one
-// combine kernel that template does not give
-__global__ __launch_bounds__(HD) void decode_shared_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
-                                                                       const int32_t* __restrict__ pos_dev, int NH, int H, int S_max, int cus,
-                                                                       int max_ranges, int shared_len) {
-    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)NH, cus);
-    if (pos < shared_len) return;
-    const int nsplit = min(sp.nsplit, max_ranges);
-    if (nsplit == 1) return;                              // the one live workgroup wrote o itself
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
-}
-
-// the instances: one per group size (OTTER_DECODE_CACHED_SHARED_MAX_GROUP of include/otter_hip.h).  f(G) with G an integral constant
-template <typename F>
-void for_group(int64_t group, F&& f) {
-    switch (group) {
-        case 2: f(std::integral_constant<int, 2>()); break;
-        case 3: f(std::integral_constant<int, 3>()); break;
-        case 4: f(std::integral_constant<int, 4>()); break;
-        case 5: f(std::integral_constant<int, 5>()); break;
-        default: f(std::integral_constant<int, 6>()); break;
-    }
-}
-
-static_assert(OTTER_DECODE_CACHED_SHARED_MAX_GROUP == 6, "decode_cache_shared.hip: one instance per group size up to the header's limit");
-
-// the two checks of the grouping: they follow the shape's
-int require_groups(const char* name, int64_t N, int64_t group) {
-    OTTER_REQUIRE(group >= 2 && group <= OTTER_DECODE_CACHED_SHARED_MAX_GROUP, "%s: group=%ld: the kernel is built for groups of 2 to %d rows", name,
-                  (long)group, OTTER_DECODE_CACHED_SHARED_MAX_GROUP);
-    OTTER_REQUIRE(N % group == 0, "%s: N=%ld rows are not whole groups of %ld", name, (long)N, (long)group);
-    return OTTER_OK;
-}
-
 }  // namespace
 
 // the checks of both entry points are decode_cache.hip's, in its order (the first failing check names the error), with the two checks of the
@@ -261,7 +229,7 @@ int otter_decode_attn_cached_shared(const void* q, int64_t q_row_stride, int64_t
     if (int e = require_capacity(name, S_max)) return e;
     if (int e = require_groups(name, N, group)) return e;
     if (int e = require_position(name, pos, S_max)) return e;
-    OTTER_REQUIRE(shared_len >= 1 && shared_len <= pos, "%s: shared_len=%ld outside [1, pos] with pos=%ld", name, (long)shared_len, (long)pos);
+    if (int e = require_shared_len(name, shared_len, pos)) return e;
     if (int e = require_token_and_cache_aligned(name, a)) return e;
     if (int e = require_cache_layout(name, &a, a, 8, S_max, HD)) return e;
     if (int e = require_row_strides(name, a, &cos_row_stride, pos)) return e;
@@ -293,8 +261,7 @@ int otter_decode_attn_cached_shared_dyn(const void* q, int64_t q_row_stride, int
     if (int e = require_shape(name, head_dim, HD, N, H)) return e;
     if (int e = require_capacity(name, S_max)) return e;
     if (int e = require_groups(name, N, group)) return e;
-    OTTER_REQUIRE(shared_len >= 1 && shared_len < S_max, "%s: shared_len=%ld outside [1, S_max) with S_max=%ld", name, (long)shared_len,
-                  (long)S_max);
+    if (int e = require_shared_len_dyn(name, shared_len, S_max)) return e;
     if (int e = require_token_and_cache_aligned(name, a)) return e;
     if (int e = require_pos_dev_aligned(name, pos_dev)) return e;
     if (int e = require_cache_layout(name, &a, a, 8, S_max, HD)) return e;
@@ -311,10 +278,7 @@ int otter_decode_attn_cached_shared_dyn(const void* q, int64_t q_row_stride, int
                               hipLaunchKernelGGL(decode_shared_dyn_kernel<decltype(G)::value>, grid, dim3(NT), 0, st, a, d.pos_dev, d.S_max, d.cus, d.table_rs);
                           });
                       },
-                      [NH](dim3 grid, hipStream_t st, const DsArgs& a, const DynStep& d) {
-                          hipLaunchKernelGGL(decode_shared_dyn_combine_kernel, grid, dim3(HD), 0, st, (const float*)a.part, a.o, d.pos_dev, (int)NH, a.H,
-                                             d.S_max, d.cus, d.max_ranges, a.shared_len);
-                      });
+                      SharedDynCombine<HD, KEYS_PER_ITER>{NH});
 }
 
 }  // extern "C"

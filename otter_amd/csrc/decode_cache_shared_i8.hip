@@ -10,16 +10,18 @@
 //   shared_len <= j < pos    per query, through `src` (NULL: the row's own), entries clamped to [0, N) as in decode_cache_i8.hip
 //   j == pos                 the new tokens in their dequantised form: the workgroup's own copy of every row's codes and scales (LDS)
 //
-// Each row appends its codes and both scales into its OWN slot [n, h, pos]; key_valid is read per row.  THE FORMAT, the quantiser (fp64
-// rotated() with one rounding, amax / 127 or 1, plain `/`, rintf, clamp), the score fmaf(s, k_scale, slope * (j - pos)) and the p * v_scale
-// update are decode_cache_i8.hip's, line for line: the stored codes and scales are bit-equal to that kernel's and to quantize_kv_int8.
+// Each row appends its codes and both scales into its OWN slot [n, h, pos]; key_valid is read per row.  THE FORMAT (kv_i8_scale, kv_i8_code),
+// the unpacking (Codes, unpack_codes) and the p * v_scale update (softmax_update_scaled) are csrc/decode_split.h's, shared with
+// decode_cache_i8.hip; the new-token step around the quantiser (fp64 rotated() with one rounding, the amax over two waves) and the score
+// fmaf(s, k_scale, slope * (j - pos)) are written as in that file: the stored codes and scales are bit-equal to that kernel's and to
+// quantize_kv_int8.  DsqArgs' fields, every check, the switch over the group size and the combine kernels are csrc/decode_cached_entry.h's.
 //
 // THE INVARIANT THE IN-PLACE UPDATE RESTS ON is decode_cache_shared.hip's, extended to the scales: no workgroup reads a slot (codes or scale)
 // that this launch writes.  The writes are slot [n, :, pos] of every row n; the reads through `src` are of keys j < pos; the shared reads are
 // of the leaders' keys j < shared_len, and the entry points require 1 <= shared_len <= pos, so a leader's write (slot pos >= shared_len) never
 // meets a shared read.  (The dyn kernel returns when the position it reads is below shared_len, as it does for one outside [1, S_max).)
 //
-// Shape: the split-key step of csrc/decode_split.h, included unchanged -- grid (key range, head, SENTENCE), 256 threads.  LANE GEOMETRY: 16
+// Shape: the split-key step of csrc/decode_split.h -- grid (key range, head, SENTENCE), 256 threads.  LANE GEOMETRY: 16
 // lanes per key, 8 codes per lane (one 8-byte load each of K and V codes), 16 groups, two keys per group in flight = 32 keys per iteration.
 // The int8 file's own geometry (8 lanes x 16 codes, 64 keys per iteration) costs 32 VGPRs of q + acc per query: with it the instances for
 // groups of 5 and 6 rows do not fit 256 VGPRs without scratch, and the rule is one geometry for every group size (DESIGN.md 4.20 has the
@@ -36,40 +38,18 @@ namespace {
 constexpr int HD = 128, LANES = 16, GROUPS = NT / LANES, KEYS_PER_ITER = GROUPS * UNROLL, DPL = HD / LANES;
 constexpr int STAGE = 2;                                  // iterations whose shared loads are issued together, one stage ahead of the arithmetic
 
-struct DsqArgs : NewTokenArgs {                           // (decode_cached_entry.h: q / k / v of the new tokens, the rotary rows)
-    int8_t* kc; int64_t kc_rs, kc_hs;                     // codes [row, h, key, 128]: row / head strides, key stride 128
-    int8_t* vc; int64_t vc_rs, vc_hs;
-    float* ks; int64_t ks_rs, ks_hs;                      // scales [row, h, key]: row / head strides, key stride 1
-    float* vs; int64_t vs_rs, vs_hs;
-    const int32_t* src; int64_t src_rs;                   // [N, >= pos] or null (= the row's own); columns < shared_len are not read
-    const uint8_t* kvalid; int64_t kv_rs;                 // [N, >= pos + 1] or null
-    const float* slopes;                                  // [H] or null
-    bf16_t* o;                                            // [N, H * 128]
-    float* part;                                          // [N * H * part_stride, PART] (nsplit > 1), part_stride >= nsplit
-    int N, H, pos, nsplit, kps, part_stride;
+struct DsqArgs : I8StepArgs {                             // (decode_cached_entry.h; columns < shared_len of `src` are not read)
     int shared_len;
     float scale;
 };
 
-// a lane's DPL codes of one vector: one load of DPL bytes
-struct __attribute__((aligned(DPL))) Codes { uint32_t w[DPL / 4]; };
-
-// DPL int8 codes -> DPL floats (exact)
-__device__ __forceinline__ void unpack_codes(const Codes& r, float (&v)[DPL]) {
-#pragma unroll
-    for (int i = 0; i < DPL / 4; ++i) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) v[4 * i + b] = (float)(int)(int8_t)(r.w[i] >> (8 * b));
-    }
-}
-
 // a key of the leader's row as a lane holds it: its share of the K and V codes, the key's two scales
-struct SharedKey { Codes k, v; float ks, vs; };
+struct SharedKey { Codes<DPL> k, v; float ks, vs; };
 
 // one key of the G queries: its score against each, the key scale, ALiBi, the rows' masks, one online-softmax update each with the value
 // scale.  kr, vr, ksc, vsc: G entries, one per query; ONE: the key is the same vector for every query (one entry), unpacked once
 template <int G, bool ONE>
-__device__ __forceinline__ void shared_i8_key_update(const Codes* kr, const Codes* vr, const float* ksc, const float* vsc,
+__device__ __forceinline__ void shared_i8_key_update(const Codes<DPL>* kr, const Codes<DPL>* vr, const float* ksc, const float* vsc,
                                                      const float (&q)[G][DPL], const int j, const bool live, const float bias,
                                                      const uint8_t* (&kv)[G], float (&m)[G], float (&l)[G], float (&acc)[G][DPL]) {
     float k[DPL], v[DPL];
@@ -89,15 +69,7 @@ __device__ __forceinline__ void shared_i8_key_update(const Codes* kr, const Code
         s = group_sum<LANES>(s);                          // (all lanes: the shuffles stay convergent)
         s = fmaf(s, ksc[ONE ? 0 : b], bias);
         if (!live || (kv[b] && kv[b][j] == 0)) s = -INFINITY;
-        const float mn = fmaxf(m[b], s);                  // (the update of decode_cache_i8.hip, with the value scale)
-        if (mn != -INFINITY) {
-            const float alpha = __expf(m[b] - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
-            const float pv = p * vsc[ONE ? 0 : b];
-            l[b] = fmaf(l[b], alpha, p);
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) acc[b][i] = fmaf(acc[b][i], alpha, pv * v[i]);
-            m[b] = mn;
-        }
+        softmax_update_scaled(m[b], l[b], acc[b], s, v, vsc[ONE ? 0 : b]);
     }
 }
 
@@ -134,8 +106,8 @@ __device__ __forceinline__ void decode_shared_i8_body(const DsqArgs& a, const in
 #pragma unroll
         for (int b = 0; b < G; ++b) {
             const float amax = fmaxf(wave_amax[b][tid < HD ? 0 : 2], wave_amax[b][tid < HD ? 1 : 3]);
-            const float sc = amax == 0.f ? 1.f : amax / 127.f;
-            const float c = fminf(fmaxf(rintf(x[b] / sc), -127.f), 127.f);
+            const float sc = kv_i8_scale(amax);
+            const float c = kv_i8_code(x[b], sc);
             code_new[b][which][d] = (int8_t)(int)c;
             if (d == 0) scale_new[b][which] = sc;
         }
@@ -151,7 +123,7 @@ __device__ __forceinline__ void decode_shared_i8_body(const DsqArgs& a, const in
             const int b = tid / (2 * LANES), n = n0 + b;
             const bool is_k = (tid & (2 * LANES - 1)) < LANES;
             int8_t* dst = (is_k ? a.kc + n * a.kc_rs + h * a.kc_hs : a.vc + n * a.vc_rs + h * a.vc_hs) + (int64_t)pos * HD + DPL * ln;
-            *reinterpret_cast<Codes*>(dst) = *reinterpret_cast<const Codes*>(&code_new[b][is_k ? 0 : 1][DPL * ln]);
+            *reinterpret_cast<Codes<DPL>*>(dst) = *reinterpret_cast<const Codes<DPL>*>(&code_new[b][is_k ? 0 : 1][DPL * ln]);
         } else if (tid < 2 * LANES * G + 2 * G) {
             const int w = tid - 2 * LANES * G, b = w >> 1, n = n0 + b;
             float* dst = (w & 1) == 0 ? a.ks + n * a.ks_rs + h * a.ks_hs : a.vs + n * a.vs_rs + h * a.vs_hs;
@@ -198,8 +170,8 @@ __device__ __forceinline__ void decode_shared_i8_body(const DsqArgs& a, const in
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
                     const int j = jb + i * KEYS_PER_ITER + u * GROUPS + g;
-                    sk[i][u].k = *reinterpret_cast<const Codes*>(kl + (int64_t)j * HD);
-                    sk[i][u].v = *reinterpret_cast<const Codes*>(vl + (int64_t)j * HD);
+                    sk[i][u].k = *reinterpret_cast<const Codes<DPL>*>(kl + (int64_t)j * HD);
+                    sk[i][u].v = *reinterpret_cast<const Codes<DPL>*>(vl + (int64_t)j * HD);
                     sk[i][u].ks = ksl[j];
                     sk[i][u].vs = vsl[j];
                 }
@@ -237,11 +209,11 @@ __device__ __forceinline__ void decode_shared_i8_body(const DsqArgs& a, const in
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
             const int j = jb + u * GROUPS + g;
-            Codes kr[G], vr[G];
+            Codes<DPL> kr[G], vr[G];
             float ksc[G], vsc[G];
             if (j < j1 && j < shared_len) {               // shared: one load (j < shared_len <= pos)
-                kr[0] = *reinterpret_cast<const Codes*>(kl + (int64_t)j * HD);
-                vr[0] = *reinterpret_cast<const Codes*>(vl + (int64_t)j * HD);
+                kr[0] = *reinterpret_cast<const Codes<DPL>*>(kl + (int64_t)j * HD);
+                vr[0] = *reinterpret_cast<const Codes<DPL>*>(vl + (int64_t)j * HD);
                 ksc[0] = ksl[j];
                 vsc[0] = vsl[j];
 #pragma unroll
@@ -256,16 +228,16 @@ __device__ __forceinline__ void decode_shared_i8_body(const DsqArgs& a, const in
                 for (int b = 0; b < G; ++b) {
                     // a table entry outside [0, N) is clamped: it can make the result wrong, never an access outside the cache
                     const int64_t row = src[b] ? (int64_t)min(max(src[b][j], 0), a.N - 1) : (int64_t)(n0 + b);
-                    kr[b] = *reinterpret_cast<const Codes*>(kb + row * a.kc_rs + (int64_t)j * HD);
-                    vr[b] = *reinterpret_cast<const Codes*>(vb + row * a.vc_rs + (int64_t)j * HD);
+                    kr[b] = *reinterpret_cast<const Codes<DPL>*>(kb + row * a.kc_rs + (int64_t)j * HD);
+                    vr[b] = *reinterpret_cast<const Codes<DPL>*>(vb + row * a.vc_rs + (int64_t)j * HD);
                     ksc[b] = ksb[row * a.ks_rs + j];
                     vsc[b] = vsb[row * a.vs_rs + j];
                 }
             } else if (j < j1) {                          // j == pos: the new tokens, as the cache now holds them
 #pragma unroll
                 for (int b = 0; b < G; ++b) {
-                    kr[b] = *reinterpret_cast<const Codes*>(&code_new[b][0][DPL * ln]);
-                    vr[b] = *reinterpret_cast<const Codes*>(&code_new[b][1][DPL * ln]);
+                    kr[b] = *reinterpret_cast<const Codes<DPL>*>(&code_new[b][0][DPL * ln]);
+                    vr[b] = *reinterpret_cast<const Codes<DPL>*>(&code_new[b][1][DPL * ln]);
                     ksc[b] = scale_new[b][0];
                     vsc[b] = scale_new[b][1];
                 }
@@ -311,52 +283,8 @@ __global__ __launch_bounds__(NT) void decode_shared_i8_dyn_kernel(DsqArgs a, con
                              a.cs ? a.sn + (int64_t)pos * table_rs : nullptr);
 }
 
-// decode_shared_dyn_combine_kernel of decode_cache_shared.hip (NH given: it is not N * H here; the return below shared_len)
-__global__ __launch_bounds__(HD) void decode_shared_i8_dyn_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ o,
-                                                                          const int32_t* __restrict__ pos_dev, int NH, int H, int S_max, int cus,
-                                                                          int max_ranges, int shared_len) {
-    DYN_POSITION_OR_RETURN(KEYS_PER_ITER, pos, sp, pos_dev, S_max, (int64_t)NH, cus);
-    if (pos < shared_len) return;
-    const int nsplit = min(sp.nsplit, max_ranges);
-    if (nsplit == 1) return;                              // the one live workgroup wrote o itself
-    const int64_t nh = (int64_t)blockIdx.y * H + blockIdx.x;
-    combine_ranges<HD>(part, o, nh, nsplit, max_ranges);
-}
-
-// the instances: one per group size (OTTER_DECODE_CACHED_SHARED_MAX_GROUP of include/otter_hip.h).  f(G) with G an integral constant
-template <typename F>
-void for_group(int64_t group, F&& f) {
-    switch (group) {
-        case 2: f(std::integral_constant<int, 2>()); break;
-        case 3: f(std::integral_constant<int, 3>()); break;
-        case 4: f(std::integral_constant<int, 4>()); break;
-        case 5: f(std::integral_constant<int, 5>()); break;
-        default: f(std::integral_constant<int, 6>()); break;
-    }
-}
-
-static_assert(OTTER_DECODE_CACHED_SHARED_MAX_GROUP == 6, "decode_cache_shared_i8.hip: one instance per group size up to the header's limit");
 static_assert(2 * LANES * OTTER_DECODE_CACHED_SHARED_MAX_GROUP + 2 * OTTER_DECODE_CACHED_SHARED_MAX_GROUP <= NT,
               "decode_cache_shared_i8.hip: the append has a thread per store");
-
-// the two checks of the grouping (decode_cache_shared.hip's) and the two of the scales (decode_cache_i8.hip's)
-int require_groups(const char* name, int64_t N, int64_t group) {
-    OTTER_REQUIRE(group >= 2 && group <= OTTER_DECODE_CACHED_SHARED_MAX_GROUP, "%s: group=%ld: the kernel is built for groups of 2 to %d rows", name,
-                  (long)group, OTTER_DECODE_CACHED_SHARED_MAX_GROUP);
-    OTTER_REQUIRE(N % group == 0, "%s: N=%ld rows are not whole groups of %ld", name, (long)N, (long)group);
-    return OTTER_OK;
-}
-
-int require_scales_aligned(const char* name, const DsqArgs& a) {
-    OTTER_REQUIRE((((uintptr_t)a.ks | (uintptr_t)a.vs) & 3) == 0, "%s: k_scale, v_scale need 4-byte alignment", name);
-    return OTTER_OK;
-}
-
-int require_scale_head_strides(const char* name, const DsqArgs& a, int64_t S_max) {
-    OTTER_REQUIRE(a.ks_hs >= S_max && a.vs_hs >= S_max && a.ks_rs >= 0 && a.vs_rs >= 0,
-                  "%s: a scale head stride below S_max would make the scales of two heads overlap", name);
-    return OTTER_OK;
-}
 
 }  // namespace
 
@@ -374,13 +302,12 @@ int otter_decode_attn_cached_shared_i8(const void* q, int64_t q_row_stride, int6
                                        void* o, void* workspace, int64_t workspace_bytes, int64_t N, int64_t H, int64_t pos, int64_t S_max,
                                        int64_t head_dim, float scale, int64_t group, int64_t shared_len, void* stream) {
     static const char name[] = "decode_attn_cached_shared_i8";
-    DsqArgs a = {{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
-                  v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
-                 (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
-                 k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
-                 src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H};
-    a.shared_len = (int)shared_len;
-    a.scale = scale;
+    DsqArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                   v_new_row_stride, v_new_head_stride, cos_rows, sin_rows, cos_row_stride},
+                  (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
+                  k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
+                  src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                 (int)shared_len, scale};
     if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, o, workspace})) return e;
     if (int e = require_cos_sin_pair(name, cos_rows, sin_rows, "rows")) return e;
     if (int e = require_shape(name, head_dim, HD, N, H)) return e;
@@ -391,7 +318,7 @@ int otter_decode_attn_cached_shared_i8(const void* q, int64_t q_row_stride, int6
     if (int e = require_cache_layout(name, &a, a, 16, S_max, HD)) return e;
     if (int e = require_scale_head_strides(name, a, S_max)) return e;
     if (int e = require_position(name, pos, S_max)) return e;
-    OTTER_REQUIRE(shared_len >= 1 && shared_len <= pos, "%s: shared_len=%ld outside [1, pos] with pos=%ld", name, (long)shared_len, (long)pos);
+    if (int e = require_shared_len(name, shared_len, pos)) return e;
     if (int e = require_row_strides(name, a, &cos_row_stride, pos)) return e;
     if (int e = require_workspace(name, workspace_bytes, OTTER_DECODE_CACHED_SHARED_I8_WORKSPACE_BYTES(N, H, pos + 1))) return e;
 
@@ -413,20 +340,18 @@ int otter_decode_attn_cached_shared_i8_dyn(const void* q, int64_t q_row_stride, 
                                            const int32_t* pos_dev, int64_t S_max, int64_t head_dim, float scale, int64_t group, int64_t shared_len,
                                            void* stream) {
     static const char name[] = "decode_attn_cached_shared_i8_dyn";
-    DsqArgs a = {{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
-                  v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
-                 (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
-                 k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
-                 src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H};
-    a.shared_len = (int)shared_len;
-    a.scale = scale;
+    DsqArgs a = {{{(const bf16_t*)q, q_row_stride, q_head_stride, (const bf16_t*)k_new, k_new_row_stride, k_new_head_stride, (const bf16_t*)v_new,
+                   v_new_row_stride, v_new_head_stride, cos_table, sin_table, 0},
+                  (int8_t*)k_cache, k_cache_row_stride, k_cache_head_stride, (int8_t*)v_cache, v_cache_row_stride, v_cache_head_stride,
+                  k_scale, k_scale_row_stride, k_scale_head_stride, v_scale, v_scale_row_stride, v_scale_head_stride,
+                  src, src_row_stride, key_valid, key_valid_row_stride, alibi_slopes, (bf16_t*)o, (float*)workspace, (int)N, (int)H},
+                 (int)shared_len, scale};
     if (int e = require_pointers(name, {q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, o, workspace, pos_dev})) return e;
     if (int e = require_cos_sin_pair(name, cos_table, sin_table, "table")) return e;
     if (int e = require_shape(name, head_dim, HD, N, H)) return e;
     if (int e = require_capacity(name, S_max)) return e;
     if (int e = require_groups(name, N, group)) return e;
-    OTTER_REQUIRE(shared_len >= 1 && shared_len < S_max, "%s: shared_len=%ld outside [1, S_max) with S_max=%ld", name, (long)shared_len,
-                  (long)S_max);
+    if (int e = require_shared_len_dyn(name, shared_len, S_max)) return e;
     if (int e = require_token_and_cache_aligned(name, a)) return e;
     if (int e = require_scales_aligned(name, a)) return e;
     if (int e = require_cache_layout(name, &a, a, 16, S_max, HD)) return e;
@@ -446,10 +371,7 @@ int otter_decode_attn_cached_shared_i8_dyn(const void* q, int64_t q_row_stride, 
                                                  d.table_rs);
                           });
                       },
-                      [NH](dim3 grid, hipStream_t st, const DsqArgs& a, const DynStep& d) {
-                          hipLaunchKernelGGL(decode_shared_i8_dyn_combine_kernel, grid, dim3(HD), 0, st, (const float*)a.part, a.o, d.pos_dev, (int)NH,
-                                             a.H, d.S_max, d.cus, d.max_ranges, a.shared_len);
-                      });
+                      SharedDynCombine<HD, KEYS_PER_ITER>{NH});
 }
 
 }  // extern "C"

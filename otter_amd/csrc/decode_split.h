@@ -1,8 +1,9 @@
 // decode_split.h -- the one statement of the DEVICE half of the split-key (flash-decoding) decode kernels: persimmon_decode.hip,
-// persimmon_decode_cache.hip, decode_cache.hip, decode_cache_i8.hip, decode_cache_shared.hip.  Each of them keeps its Args struct, its key loop
-// (the loaders and the score terms differ: strided past + copy-out, cache through the `src` table, codes + scales, a shared prompt; ALiBi or
-// none, key scale or none) and its attention kernels.  The HOST half of the four cached files (argument checks, shared Args fields, combine
-// kernels, launch sequence) is decode_cached_entry.h, which includes this header; the rest is here:
+// persimmon_decode_cache.hip, decode_cache.hip, decode_cache_i8.hip, decode_cache_shared.hip, decode_cache_shared_i8.hip.  Each of them keeps
+// its Args struct, its key loop (the loaders and the score terms differ: strided past + copy-out, cache through the `src` table, codes +
+// scales, a shared prompt over either cache; ALiBi or none, key scale or none) and its attention kernels.  The HOST half of the five cached
+// files (argument checks, shared Args fields, combine kernels, launch sequence) is decode_cached_entry.h, which includes this header; the
+// rest is here, the int8 cache's format (Codes, unpack_codes, kv_i8_scale, kv_i8_code) included:
 //
 //   grid (key range, head, row), NT = 256 threads.  A group of LANES lanes owns one key at a time, UNROLL keys per group in flight: score by
 //   a LANES-wide butterfly (group_sum), online softmax per group (softmax_update: running max m, sum l, o[W]) -- no score buffer, no LDS
@@ -103,6 +104,28 @@ __device__ __forceinline__ void unpack8(const uint4& r, float (&v)[8]) {
     }
 }
 
+// ---- the int8 cache (decode_cache_i8.hip, decode_cache_shared_i8.hip) -------------------------------------------------------------------
+// a lane's DPL codes of one cached vector: one load of DPL bytes (8 or 16)
+template <int DPL>
+struct __attribute__((aligned(DPL))) Codes { uint32_t w[DPL / 4]; };
+
+// DPL int8 codes -> DPL floats (exact)
+template <int DPL>
+__device__ __forceinline__ void unpack_codes(const Codes<DPL>& r, float (&v)[DPL]) {
+#pragma unroll
+    for (int i = 0; i < DPL / 4; ++i) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v[4 * i + b] = (float)(int)(int8_t)(r.w[i] >> (8 * b));
+    }
+}
+
+// THE FORMAT (otter_amd/kv_cache.py states it once for the project; quantize_kv_int8 there must agree with these two bit for bit): for the
+// vector x[128] the bf16 cache would hold (k after rotary, rounded once to bf16; v as given), read as fp32:
+//   amax = max |x[i]|;  scale = amax / 127 (1 when amax == 0);  code = clamp(rint(x[i] / scale), -127, 127);  value = code * scale.
+// Plain `/` and rintf (round-half-even): IEEE-exact ops, the same codes and scales as torch computes.  No reciprocal.
+__device__ __forceinline__ float kv_i8_scale(const float amax) { return amax == 0.f ? 1.f : amax / 127.f; }
+__device__ __forceinline__ float kv_i8_code(const float x, const float sc) { return fminf(fmaxf(rintf(x / sc), -127.f), 127.f); }
+
 // double -> bf16, round-to-nearest-even in ONE rounding: (float)y is RNE already; it misleads the second rounding only when it lands exactly
 // on a bf16 midpoint that y itself was not on -- then the float is moved one step towards y first.
 __device__ __forceinline__ bf16_t d2bf(double y) {
@@ -126,8 +149,7 @@ __device__ __forceinline__ double rotated(const bf16_t* x, const float* cs, cons
 // one key into a group's online softmax: score s (the same in every lane of the group; -inf for a masked key or a slot past the range, which
 // then adds nothing), this lane's W dims of the value.  While nothing has been added m stays -inf and l, acc stay 0.  m and l go in and come
 // back BY VALUE (m = r.m; l = r.l; at the call): passed by reference they are promoted to registers only after inlining, which reorders the
-// key loop's phis and with them the register assignment.  (decode_cache_i8.hip, 16 codes per lane times the key's value scale, keeps its
-// update written out: no form of this function left its kernels' assembly as it was.)  The fields are in the order (l, m), against the
+// key loop's phis and with them the register assignment.  The fields are in the order (l, m), against the
 // parameters' (m, l), on purpose: it is the order of the two merge phis after the `if`, and with (m, l) the two moves that end a key's
 // update come out swapped.  Name the fields at every use; `{l, m}` below is the only positional initialiser.
 struct Softmax { float l, m; };
@@ -143,6 +165,23 @@ __device__ __forceinline__ Softmax softmax_update(const float m, const float l, 
         r.m = mn;
     }
     return r;
+}
+
+// the same over the int8 cache: v are the key's value CODES, v_scale its value scale -- acc += (p * v_scale) * code.  m and l BY REFERENCE:
+// the caller, decode_cache_shared_i8.hip's shared_i8_key_update, is itself an inlined function over m[G], l[G], and the by-value form above
+// changes 10 of its 12 kernels.  decode_cache_i8.hip (16 codes per lane) keeps these statements WRITTEN OUT in its key loop, a second copy to
+// keep in step by hand: neither form of this function left its two attention kernels as they were (1327 -> 1338 instruction lines).
+template <int W>
+__device__ __forceinline__ void softmax_update_scaled(float& m, float& l, float (&acc)[W], const float s, const float (&v)[W], const float v_scale) {
+    const float mn = fmaxf(m, s);
+    if (mn != -INFINITY) {
+        const float alpha = __expf(m - mn), p = __expf(s - mn);   // exp(-inf) = 0 for an empty history / a masked key
+        const float pv = p * v_scale;
+        l = fmaf(l, alpha, p);
+#pragma unroll
+        for (int i = 0; i < W; ++i) acc[i] = fmaf(acc[i], alpha, pv * v[i]);
+        m = mn;
+    }
 }
 
 // the GROUPS groups of a workgroup, in group order.  Thread of group g whose acc[W] are dims d0 .. d0 + W - 1 (g, d0 from the caller, whose

@@ -365,14 +365,8 @@ class StaticKVCache:
         lever is "1" the kernel is taken only from SHARED_KERNEL_MIN_KEYS shared keys per head on (sentences x shared_len): below that the
         step is bound by latency and the grouped kernel, with a third of the workgroups, measured 3.5 % slower.  All of this
         is fixed for a whole generate call, so a captured step keeps its kernel."""
-        lever = os.environ.get("OTTER_SHARED_PREFIX", "")
-        if self.group < 2 or self.shared_len < 1 or self.int8 or lever == "0":
-            return False
-        if lever != "1" and (self.rows // self.group) * self.shared_len < SHARED_KERNEL_MIN_KEYS:
-            return False
-        from . import ops
-
-        return self.group in ops.DECODE_CACHED_SHARED_GROUPS and self.uses_kernel(q, n_kv)
+        return not self.int8 and self._uses_grouped_kernel(q, n_kv, os.environ.get("OTTER_SHARED_PREFIX", ""), SHARED_KERNEL_MIN_KEYS,
+                                                           "DECODE_CACHED_SHARED_GROUPS")
 
     def uses_shared_i8_kernel(self, q: torch.Tensor, n_kv: int) -> bool:
         """The step runs on csrc/decode_cache_shared_i8.hip: an int8 cache with a shared prompt in a group size that kernel is built for,
@@ -380,14 +374,21 @@ class StaticKVCache:
         (this kernel's own A/B lever: "0" keeps csrc/decode_cache_i8.hip, through the table).  Unless OTTER_SHARED_PREFIX_I8 is "1" the kernel
         is taken only from SHARED_I8_KERNEL_MIN_KEYS shared keys per head on (sentences x shared_len).  OTTER_SHARED_PREFIX=1 does not force
         it.  All of this is fixed for a whole generate call, so a captured step keeps its kernel."""
-        lever = os.environ.get("OTTER_SHARED_PREFIX_I8", "")
-        if not self.int8 or self.group < 2 or self.shared_len < 1 or lever == "0" or os.environ.get("OTTER_SHARED_PREFIX", "") == "0":
+        if os.environ.get("OTTER_SHARED_PREFIX", "") == "0":
             return False
-        if lever != "1" and (self.rows // self.group) * self.shared_len < SHARED_I8_KERNEL_MIN_KEYS:
+        return self.int8 and self._uses_grouped_kernel(q, n_kv, os.environ.get("OTTER_SHARED_PREFIX_I8", ""), SHARED_I8_KERNEL_MIN_KEYS,
+                                                       "DECODE_CACHED_SHARED_I8_GROUPS")
+
+    def _uses_grouped_kernel(self, q: torch.Tensor, n_kv: int, lever: str, min_keys: int, groups: str) -> bool:
+        """The rule the two grouped kernels share: a shared prompt, the kernel's lever not "0", `min_keys` shared keys per head (sentences x
+        shared_len) unless the lever is "1", a group size in `ops.<groups>`, and `uses_kernel`."""
+        if self.group < 2 or self.shared_len < 1 or lever == "0":
+            return False
+        if lever != "1" and (self.rows // self.group) * self.shared_len < min_keys:
             return False
         from . import ops
 
-        return self.group in ops.DECODE_CACHED_SHARED_I8_GROUPS and self.uses_kernel(q, n_kv)
+        return self.group in getattr(ops, groups) and self.uses_kernel(q, n_kv)
 
     def attend(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
         """One cached step of `layer` at position `length` (which the caller advances once per forward, after the last layer):
@@ -395,44 +396,25 @@ class StaticKVCache:
         key_valid uint8 / bool [N, length+1] or None; slopes fp32 [H] or None.  Returns o [N, H*d] in q's dtype.
         Replay mode: the position is `pos_dev`, cos / sin are the whole fp32 tables [>= max_len, d] (or None) and the mask is the cache's
         own `valid` (key_valid must be None)."""
+        if self.replay and key_valid is not None:
+            raise ValueError("StaticKVCache.attend: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
+        n_kv = k_new.shape[1]
+        if not self.uses_kernel(q, n_kv):
+            if self.replay:
+                self.kernel_steps = False   # (the restatement reads the position back to the host: such a step cannot be captured)
+            return self.attend_reference(layer, q, k_new, v_new, scale, cos=cos, sin=sin, key_valid=key_valid, slopes=slopes)
+        from . import ops
+
+        # ONE choice of the op: over the int8 cache or not, grouped or through the table, with the position in device memory or not.  (Looked
+        # up on `ops` at the call: the tests put stand-ins there.)
+        grouped = self.uses_shared_i8_kernel(q, n_kv) if self.int8 else self.uses_shared_kernel(q, n_kv)
+        op = getattr(ops, "decode_attn_cached" + ("_shared" if grouped else "") + ("_i8" if self.int8 else "") + ("_dyn" if self.replay else ""))
+        caches = (self.k[layer], self.v[layer]) + ((self.k_scale[layer], self.v_scale[layer]) if self.int8 else ())
+        grouping = (self.group, self.shared_len) if grouped else ()
         if self.replay:
-            if key_valid is not None:
-                raise ValueError("StaticKVCache.attend: in replay mode the mask is the cache's own (`valid`); pass key_valid=None")
-            if self.uses_kernel(q, k_new.shape[1]):
-                from . import ops
-
-                if self.uses_shared_i8_kernel(q, k_new.shape[1]):
-                    return ops.decode_attn_cached_shared_i8_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer],
-                                                                self.v_scale[layer], self.pos_dev, scale, self.group, self.shared_len,
-                                                                cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid, slopes=slopes)
-                if self.int8:
-                    return ops.decode_attn_cached_i8_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
-                                                         self.pos_dev, scale, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
-                                                         slopes=slopes)
-                if self.uses_shared_kernel(q, k_new.shape[1]):
-                    return ops.decode_attn_cached_shared_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.pos_dev, scale, self.group,
-                                                             self.shared_len, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
-                                                             slopes=slopes)
-                return ops.decode_attn_cached_dyn(q, k_new, v_new, self.k[layer], self.v[layer], self.pos_dev, scale, cos_table=cos,
-                                                  sin_table=sin, src=self.src, key_valid=self.valid, slopes=slopes)
-            self.kernel_steps = False   # (the restatement reads the position back to the host: such a step cannot be captured)
-            return self.attend_reference(layer, q, k_new, v_new, scale, cos=cos, sin=sin, slopes=slopes)
-        if self.uses_kernel(q, k_new.shape[1]):
-            from . import ops
-
-            if self.uses_shared_i8_kernel(q, k_new.shape[1]):
-                return ops.decode_attn_cached_shared_i8(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
-                                                        self.length, scale, self.group, self.shared_len, cos=cos, sin=sin, src=self.src,
-                                                        key_valid=key_valid, slopes=slopes)
-            if self.int8:
-                return ops.decode_attn_cached_i8(q, k_new, v_new, self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer],
-                                                 self.length, scale, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)
-            if self.uses_shared_kernel(q, k_new.shape[1]):
-                return ops.decode_attn_cached_shared(q, k_new, v_new, self.k[layer], self.v[layer], self.length, scale, self.group,
-                                                     self.shared_len, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)
-            return ops.decode_attn_cached(q, k_new, v_new, self.k[layer], self.v[layer], self.length, scale, cos=cos, sin=sin, src=self.src,
-                                          key_valid=key_valid, slopes=slopes)
-        return self.attend_reference(layer, q, k_new, v_new, scale, cos=cos, sin=sin, key_valid=key_valid, slopes=slopes)
+            return op(q, k_new, v_new, *caches, self.pos_dev, scale, *grouping, cos_table=cos, sin_table=sin, src=self.src, key_valid=self.valid,
+                      slopes=slopes)
+        return op(q, k_new, v_new, *caches, self.length, scale, *grouping, cos=cos, sin=sin, src=self.src, key_valid=key_valid, slopes=slopes)
 
     def attend_reference(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
         """What csrc/decode_cache.hip does, in plain torch on any device and dtype: rotary (fp32 at least, k rounded to the cache dtype once),

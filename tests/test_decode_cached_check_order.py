@@ -1,5 +1,5 @@
-"""CPU: the ORDER of the argument checks of the eight cached-decode entry points (csrc/decode_cache.hip, decode_cache_i8.hip,
-decode_cache_shared.hip, persimmon_decode_cache.hip) is part of the ABI: of two faults in one call, the check that stands first names the error.
+"""CPU: the ORDER of the argument checks of the ten cached-decode entry points (csrc/decode_cache.hip, decode_cache_i8.hip,
+decode_cache_shared.hip, decode_cache_shared_i8.hip, persimmon_decode_cache.hip) is part of the ABI: of two faults in one call, the check that stands first names the error.
 For each entry point CHECKS lists every check from the null-pointer check to the workspace check, in order, each with the message fragment
 that identifies it and one perturbation of an otherwise valid call that trips it.  Every perturbation is tried alone, and every adjacent
 pair (i, i + 1) together: the message must be check i's.  No GPU: every call is refused before anything is launched, so aligned dummy
@@ -19,6 +19,7 @@ TAIL = ["o", "ws", "ws_bytes", "N", "H", "pos", "S_max", "head_dim"]   # pos: th
 PLAIN = NEW_TOKEN + CACHE + TABLES + ["slopes"] + TAIL + ["scale"]
 I8 = NEW_TOKEN + CACHE + SCALES + TABLES + ["slopes"] + TAIL + ["scale"]
 SHARED = PLAIN + ["group", "shared_len"]
+SHARED_I8 = I8 + ["group", "shared_len"]
 PERSIMMON = ["qkv", "gq", "bq", "gk", "bk", "cos", "sin"] + CACHE + TABLES + TAIL + ["rot", "eps", "scale"]
 PERSIMMON_DYN = PERSIMMON[:7] + ["table_rs"] + PERSIMMON[7:]
 
@@ -81,6 +82,12 @@ CHECKS = {
                                                     ALIGNED, STRIDES_8, OVERLAP_128, ROWS, WORKSPACE]),
     "decode_attn_cached_shared_dyn": (14, SHARED, 128, [NULL, COS_SIN, HD128, SHAPE, CAPACITY, GROUP, WHOLE_GROUPS, SHARED_LEN_DYN, ALIGNED,
                                                         POS_DEV, STRIDES_8, OVERLAP_128, ROWS_DYN, WORKSPACE]),
+    "decode_attn_cached_shared_i8": (18, SHARED_I8, 128, [NULL, COS_SIN, HD128, SHAPE, CAPACITY, GROUP, WHOLE_GROUPS, ALIGNED, SCALE_ALIGNED,
+                                                          STRIDES_8_NEW, STRIDES_16, OVERLAP_128, SCALE_OVERLAP, POS_LOW, POS_HIGH, SHARED_LEN, ROWS,
+                                                          WORKSPACE]),
+    "decode_attn_cached_shared_i8_dyn": (17, SHARED_I8, 128, [NULL, COS_SIN, HD128, SHAPE, CAPACITY, GROUP, WHOLE_GROUPS, SHARED_LEN_DYN, ALIGNED,
+                                                              SCALE_ALIGNED, STRIDES_8_NEW, STRIDES_16, OVERLAP_128, SCALE_OVERLAP, POS_DEV, ROWS_DYN,
+                                                              WORKSPACE]),
     "persimmon_decode_attn_cached": (12, PERSIMMON, 64, [NULL, HD64, SHAPE, ROT, CAPACITY, POS_LOW, POS_HIGH, ALIGNED_PERSIMMON,
                                                          STRIDES_8_PERSIMMON, OVERLAP_64, ROWS_PERSIMMON, WORKSPACE]),
     "persimmon_decode_attn_cached_dyn": (11, PERSIMMON_DYN, 64, [NULL, HD64, SHAPE, ROT, CAPACITY, ALIGNED_PERSIMMON, POS_DEV,

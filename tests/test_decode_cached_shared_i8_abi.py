@@ -1,7 +1,7 @@
 """CPU: otter_decode_attn_cached_shared_i8 / _dyn (csrc/decode_cache_shared_i8.hip) validate their arguments before anything is launched --
 negative status and a message, no GPU needed -- in an order that is part of the ABI, and so do their Python bindings, on CPU tensors over a
 recording stand-in for the library.  Device pointers are never dereferenced on these paths, so aligned dummy addresses stand in for them.
-The style is tests/test_decode_cached_shared_abi.py's, the CHECKS table tests/test_decode_cached_check_order.py's."""
+The style is tests/test_decode_cached_shared_abi.py's; the order of the checks is tests/test_decode_cached_check_order.py's table."""
 import os
 import re
 
@@ -143,63 +143,7 @@ def test_workspace_one_byte_short_is_rejected(lib, entry):
     refused(lib, entry, b"%d needed" % need, ws_bytes=need - 1, **wide, **({} if entry == "dyn" else {"pos": 128}))
 
 
-# ---- the order of the checks (part of the ABI): of two faults, the one listed first names the error --------------------------------------------
-NULL = ("null pointer", dict(o=None))
-COS_SIN = ("both be given or both be NULL", dict(cos=P))
-HD128 = ("head_dim 64 (128 only)", dict(head_dim=64))
-SHAPE = ("bad shape N=6 H=0", dict(H=0))
-CAPACITY = ("S_max=1 outside [2, 65536]", dict(S_max=1))
-GROUP = ("group=9: the kernel is built for groups of 2 to 6 rows", dict(group=9))
-WHOLE_GROUPS = ("N=7 rows are not whole groups of", dict(N=7))
-ALIGNED = ("q, k_new, v_new, k_cache, v_cache need 16-byte alignment", dict(vn=P + 4 * H * 128 + 2))
-SCALE_ALIGNED = ("k_scale, v_scale need 4-byte alignment", dict(vs=P + 2))
-STRIDES_8_NEW = ("q / k_new / v_new strides must be multiples of 8 elements", dict(kn_rs=3 * H * 128 + 4))
-STRIDES_16 = ("code cache strides must be multiples of 16 elements", dict(kc_rs=H * S_MAX * 128 + 8))
-OVERLAP_128 = ("a cache head stride below S_max * 128 would make the slots of two heads overlap", dict(kc_hs=S_MAX * 128 - 16))
-SCALE_OVERLAP = ("a scale head stride below S_max would make the scales of two heads overlap", dict(ks_hs=S_MAX - 1))
-POS_LOW = ("pos=0: a cached step continues a cache", dict(pos=0))
-POS_HIGH = ("pos=64 is beyond the cache capacity S_max=64", dict(pos=S_MAX))
-SHARED_LEN = ("shared_len=0 outside [1, pos]", dict(shared_len=0))
-SHARED_LEN_DYN = ("shared_len=0 outside [1, S_max)", dict(shared_len=0))
-POS_DEV = ("pos_dev needs 4-byte alignment", dict(pos=P + 2))
-# (a negative row stride is below `pos` at every position: the perturbation holds beside the position's and shared_len's)
-ROWS = ("src needs a row stride >= pos, key_valid one >= pos + 1, cos / sin a non-negative one", dict(src=P, src_rs=-1))
-ROWS_DYN = ("cos / sin tables need a row stride >= 128, src one >= S_max - 1, key_valid one >= S_max", dict(kvalid=P, kv_rs=S_MAX - 1))
-WORKSPACE = ("workspace of 16 bytes, ", dict(ws_bytes=16))
-
-# entry -> (number of its checks, the checks).  The number stands beside the name on purpose: a check added to an entry point without an
-# entry here must fail this test.
-CHECKS = {
-    "scalar": (18, [NULL, COS_SIN, HD128, SHAPE, CAPACITY, GROUP, WHOLE_GROUPS, ALIGNED, SCALE_ALIGNED, STRIDES_8_NEW, STRIDES_16, OVERLAP_128,
-                    SCALE_OVERLAP, POS_LOW, POS_HIGH, SHARED_LEN, ROWS, WORKSPACE]),
-    "dyn": (17, [NULL, COS_SIN, HD128, SHAPE, CAPACITY, GROUP, WHOLE_GROUPS, SHARED_LEN_DYN, ALIGNED, SCALE_ALIGNED, STRIDES_8_NEW, STRIDES_16,
-                 OVERLAP_128, SCALE_OVERLAP, POS_DEV, ROWS_DYN, WORKSPACE]),
-}
-# The pair (POS_LOW, POS_HIGH) no call can hold (the two sides of 1 <= pos < S_max): tested as (i, i + 2), the one replacement
-# tests/test_decode_cached_check_order.py makes
-REPLACED = {entry: [checks.index(POS_LOW)] for entry, (_, checks) in CHECKS.items() if POS_LOW in checks}
-
-
-@pytest.mark.parametrize("entry", ENTRIES)
-def test_every_check_is_listed_and_trips_alone(lib, entry):
-    count, checks = CHECKS[entry]
-    assert len(checks) == count
-    assert len({fragment for fragment, _ in checks}) == count           # no fragment identifies two checks
-    for i, (fragment, over) in enumerate(checks):
-        assert not any(fragment in other for other, _ in checks[:i] + checks[i + 1:])
-        refused(lib, entry, fragment, over)
-
-
-@pytest.mark.parametrize("entry", ENTRIES)
-def test_of_two_adjacent_faults_the_first_names_the_error(lib, entry):
-    _, checks = CHECKS[entry]
-    replaced = REPLACED.get(entry, [])
-    assert replaced == ([13] if entry == "scalar" else [])
-    for i in range(len(checks) - 1):
-        j = i + 2 if i in replaced else i + 1
-        (fragment, over), (_, more) = checks[i], checks[j]
-        assert not set(over) & set(more), (entry, fragment)             # the two perturbations touch different arguments
-        refused(lib, entry, fragment, over, more)
+# (the order of the checks, part of the ABI, is in tests/test_decode_cached_check_order.py: the one table of all ten entry points)
 
 
 def test_workspace_formulas_match_the_header():
