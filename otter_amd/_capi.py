@@ -162,7 +162,11 @@ SIGNATURES = {
     "otter_xattn_decode": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _vp]),
     "otter_gemv_w8": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
     "otter_gemm_w8_rows": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
-    "otter_dequant_w8": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "otter_gemv_w8_gated": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp, _i64,
+                                   _vp]),
+    "otter_gemm_w8_rows_gated": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp,
+                                        _i64, _vp]),
+    "otter_dequant_w8":(_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp]),
     "otter_logits_process": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp]),
     "otter_beam_step_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "otter_beam_step": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int,

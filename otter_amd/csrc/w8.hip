@@ -7,6 +7,8 @@
 //                 and the i8 matrix instruction is not used: q is converted to bf16 in registers (exact for |q| <= 127) and fed to
 //                 v_mfma_f32_16x16x32_bf16 with x padded to 16 rows; fp32 accumulation, the scale applied to the fp32 sum.
 // otter_gemm_w8_rows  the same product for 1 <= M <= 64: one-token steps of 17 to 64 rows (B x num_beams) still stream the weight once.
+// otter_gemv_w8_gated, otter_gemm_w8_rows_gated  the same two products with y = v tanh(*gate) + R in place of the activation: the second FFN
+//                 product of a gated cross-attention block with its tanh-gate residual.  Same kernels, GATED = true.
 // otter_dequant_w8  out[n, k] = bf16(float(q[n, k]) * scale[n]): the streaming pass behind the prompt (prefill) path.
 //
 // GEMV decomposition.  A workgroup of 4 waves owns 16 R output rows (R = 1, or 2 from N = 16384 up) and one of S contiguous K ranges; its
@@ -51,6 +53,8 @@ struct W8Args {
     float* part;                          // [S, M, N] fp32 (S > 1)
     int M, N, K, act, S;
     int T, q;                             // K steps in all, K steps per wave
+    const float* gate;                    // the GATED kernels only: y = v tanh(*gate) + R, gate NULL: y = v + R (R NULL: a plain entry)
+    const void* R; int64_t ldr; int r_dtype;
 };
 
 // 8 int8 (two dwords) -> 8 bf16, exact
@@ -69,15 +73,29 @@ __device__ __forceinline__ w8_bf16x8_t cvt8(uint32_t lo, uint32_t hi) {
     return __builtin_bit_cast(w8_bf16x8_t, r);
 }
 
-__device__ __forceinline__ float w8_epilogue(float v, int64_t n, const W8Args& a) {
+// GATED (the _gated entries): y = v tanh(*gate) + R, the EPI_SCALE_RES tail of the GEMM family (gemm_tail.h), instead of the activation.  A
+// template parameter, not a test of a.R: the plain entries keep, instruction for instruction, the code they had (with a run-time branch
+// they measured up to 3 % slower where K is split).  w8_gate: the factor, once per thread.
+template <bool GATED>
+__device__ __forceinline__ float w8_gate(const W8Args& a) {
+    if constexpr (GATED) return a.gate ? tanhf(*a.gate) : 1.0f;
+    else return 1.0f;
+}
+
+template <bool GATED>
+__device__ __forceinline__ float w8_epilogue(float v, float sg, int64_t m, int64_t n, const W8Args& a) {
     v *= a.scale[n];
     if (a.bias) v += ld_as_f32(a.bias, n, a.bias_dtype);
-    if (a.act == 1) return gelu_erf(v);
-    if (a.act == 3) {                     // relu(v)^2 in fp32 on the fp32 sum: one rounding, to the output dtype, in the caller's store
-        const float r = fmaxf(v, 0.f);
-        return r * r;
+    if constexpr (GATED) {
+        return v * sg + ld_as_f32(a.R, m * a.ldr + n, a.r_dtype);
+    } else {
+        if (a.act == 1) return gelu_erf(v);
+        if (a.act == 3) {                 // relu(v)^2 in fp32 on the fp32 sum: one rounding, to the output dtype, in the caller's store
+            const float r = fmaxf(v, 0.f);
+            return r * r;
+        }
+        return v;
     }
-    return v;
 }
 
 template <int R>
@@ -85,7 +103,7 @@ struct Batch {
     uint4 w[UNROLL][R], xa[UNROLL], xb[UNROLL];
 };
 
-template <int R>
+template <int R, bool GATED>
 __global__ __launch_bounds__(NT) void gemv_w8_kernel(W8Args a) {
     __shared__ float red[WAVES][R][4][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -158,6 +176,7 @@ __global__ __launch_bounds__(NT) void gemv_w8_kernel(W8Args a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) red[wv][r][i][lane] = acc[r][i];
     __syncthreads();
+    const float sg = w8_gate<GATED>(a);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int nn = tid & 15, m = tid >> 4;                      // neighbouring threads write neighbouring columns of y
@@ -167,19 +186,20 @@ __global__ __launch_bounds__(NT) void gemv_w8_kernel(W8Args a) {
         float v = red[0][r][i][ln];
 #pragma unroll
         for (int w2 = 1; w2 < WAVES; ++w2) v += red[w2][r][i][ln];
-        if (a.S == 1) st_from_f32(a.y, (int64_t)m * a.ldy + n, a.y_dtype, w8_epilogue(v, n, a));
+        if (a.S == 1) st_from_f32(a.y, (int64_t)m * a.ldy + n, a.y_dtype, w8_epilogue<GATED>(v, sg, m, n, a));
         else a.part[((int64_t)s * a.M + m) * a.N + n] = v;
     }
 }
 
 // S > 1: one thread per output element adds the S ranges in order
+template <bool GATED>
 __global__ __launch_bounds__(NT) void gemv_w8_reduce_kernel(W8Args a) {
     const int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (e >= (int64_t)a.M * a.N) return;
     const int64_t m = e / a.N, n = e % a.N;
     float v = a.part[e];
     for (int s = 1; s < a.S; ++s) v += a.part[(int64_t)s * a.M * a.N + e];
-    st_from_f32(a.y, m * a.ldy + n, a.y_dtype, w8_epilogue(v, n, a));
+    st_from_f32(a.y, m * a.ldy + n, a.y_dtype, w8_epilogue<GATED>(v, w8_gate<GATED>(a), m, n, a));
 }
 
 // ---- rows kernel (17 to 64 rows; any 1 <= M <= 64 is accepted) -----------------------------------------------------------------------------
@@ -192,7 +212,7 @@ constexpr int ROWS_MAX_SPLIT = 8;                   // OTTER_GEMM_W8_ROWS_WORKSP
 constexpr int64_t ROWS_WG_TARGET = 256;             // K is split further only while there is at most one workgroup per CU of a 256-CU part
 constexpr int64_t ROWS_MIN_K_PER_WG = 512;
 
-template <int MB>
+template <int MB, bool GATED>
 __global__ __launch_bounds__(NT) void gemm_w8_rows_kernel(W8Args a) {          // a.T: chunks in all, a.q: chunks per K range
     __shared__ uint4 xs[2][ROWS_MAX_M * ROWS_SLOTS];                           // 2 x 32 KB
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -278,6 +298,7 @@ __global__ __launch_bounds__(NT) void gemm_w8_rows_kernel(W8Args a) {          /
         }
     }
 
+    const float sg = w8_gate<GATED>(a);
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
         const int m = 16 * mb + r16;
@@ -285,7 +306,7 @@ __global__ __launch_bounds__(NT) void gemm_w8_rows_kernel(W8Args a) {          /
         for (int i = 0; i < 4; ++i) {
             const int64_t n = n0 + 4 * g + i;
             if (m >= a.M || n >= a.N) continue;
-            if (a.S == 1) st_from_f32(a.y, (int64_t)m * a.ldy + n, a.y_dtype, w8_epilogue(acc[mb][i], n, a));
+            if (a.S == 1) st_from_f32(a.y, (int64_t)m * a.ldy + n, a.y_dtype, w8_epilogue<GATED>(acc[mb][i], sg, m, n, a));
             else a.part[((int64_t)s * a.M + m) * a.N + n] = acc[mb][i];
         }
     }
@@ -316,96 +337,156 @@ __global__ __launch_bounds__(NT) void dequant_w8_kernel(const int8_t* __restrict
     }
 }
 
+// ---- host: argument checks and launches shared by the plain and the gated entry of each family --------------------------------------------
+
+struct W8Call {
+    const void* x; int64_t ldx; const void* qweight; int64_t ldw; const float* scale; const void* bias; int bias_dtype;
+    void* y; int64_t ldy; int y_dtype; int64_t M, N, K; int act; void* workspace; int64_t workspace_bytes; void* stream;
+    bool gated; const float* gate; const void* R; int64_t ldr; int r_dtype;       // gated: the tail of otter_gemv_w8_gated (R must be there)
+};
+
+// the checks in the order include/otter_hip.h documents them; `what` names the entry in the message, max_m is 16 or 64
+int w8_check(const W8Call& c, const char* what, int max_m) {
+    OTTER_REQUIRE(c.x && c.qweight && c.scale && c.y && c.workspace && (!c.gated || c.R), "%s: null pointer", what);
+    OTTER_REQUIRE(c.M >= 1 && c.M <= max_m, "%s: M=%d outside [1, %d]", what, (int)c.M, max_m);
+    OTTER_REQUIRE(c.N >= 1 && c.N <= (int64_t)1 << 30, "%s: N=%ld outside [1, 2^30]", what, (long)c.N);
+    OTTER_REQUIRE(c.K >= 16 && c.K % 16 == 0 && c.K <= (int64_t)1 << 30, "%s: K=%d must be a positive multiple of 16", what, (int)c.K);
+    OTTER_REQUIRE(c.ldw % 16 == 0 && c.ldx % 8 == 0 && (((uintptr_t)c.x | (uintptr_t)c.qweight | (uintptr_t)c.y) & 15) == 0,
+                  "%s: alignment (x, qweight, y 16-byte aligned; ldw %% 16 == 0; ldx %% 8 == 0)", what);
+    OTTER_REQUIRE(c.ldw >= c.K && c.ldx >= c.K && c.ldy >= c.N && (!c.gated || c.ldr >= c.N),
+                  "%s: a leading dimension is smaller than the row it holds", what);
+    if (c.gated) {
+        OTTER_REQUIRE((c.y_dtype == OTTER_F32 || c.y_dtype == OTTER_BF16) && (!c.bias || c.bias_dtype == OTTER_F32 || c.bias_dtype == OTTER_BF16) &&
+                          (c.r_dtype == OTTER_F32 || c.r_dtype == OTTER_BF16),
+                      "%s: y / bias / R dtype must be OTTER_F32 or OTTER_BF16", what);
+        // y is written while other threads still read R: the two blocks may not share a byte (the same tensor included)
+        const uintptr_t y0 = (uintptr_t)c.y, y1 = y0 + (uintptr_t)((c.M - 1) * c.ldy + c.N) * (c.y_dtype == OTTER_F32 ? 4 : 2);
+        const uintptr_t r0 = (uintptr_t)c.R, r1 = r0 + (uintptr_t)((c.M - 1) * c.ldr + c.N) * (c.r_dtype == OTTER_F32 ? 4 : 2);
+        OTTER_REQUIRE(y1 <= r0 || r1 <= y0, "%s: y and R overlap", what);
+    } else {
+        OTTER_REQUIRE((c.y_dtype == OTTER_F32 || c.y_dtype == OTTER_BF16) && (!c.bias || c.bias_dtype == OTTER_F32 || c.bias_dtype == OTTER_BF16),
+                      "%s: y / bias dtype must be OTTER_F32 or OTTER_BF16", what);
+        OTTER_REQUIRE(c.act == 0 || c.act == 1 || c.act == 3, "%s: act=%d (0 none, 1 GELU, 3 squared ReLU)", what, c.act);
+    }
+    const int64_t need = OTTER_GEMV_W8_WORKSPACE_BYTES(c.M, c.N, c.K);       // (OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES is the same expression)
+    OTTER_REQUIRE(c.workspace_bytes >= need, "%s: workspace of %ld bytes, %ld needed", what, (long)c.workspace_bytes, (long)need);
+    return OTTER_OK;
+}
+
+W8Args w8_args(const W8Call& c) {
+    W8Args a;
+    a.x = (const bf16_t*)c.x; a.ldx = c.ldx;
+    a.w = (const int8_t*)c.qweight; a.ldw = c.ldw;
+    a.scale = c.scale; a.bias = c.bias; a.bias_dtype = c.bias_dtype;
+    a.y = c.y; a.ldy = c.ldy; a.y_dtype = c.y_dtype;
+    a.part = (float*)c.workspace;
+    a.M = (int)c.M; a.N = (int)c.N; a.K = (int)c.K; a.act = c.gated ? 0 : c.act;
+    a.gate = c.gated ? c.gate : nullptr;
+    a.R = c.gated ? c.R : nullptr; a.ldr = c.ldr; a.r_dtype = c.r_dtype;
+    return a;
+}
+
+template <bool GATED>
+void launch_gemv(int R, dim3 grid, hipStream_t st, const W8Args& a) {
+    if (R == 2) hipLaunchKernelGGL((gemv_w8_kernel<2, GATED>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((gemv_w8_kernel<1, GATED>), grid, dim3(NT), 0, st, a);
+}
+
+template <bool GATED>
+void launch_rows(int mb, dim3 grid, hipStream_t st, const W8Args& a) {
+    switch (mb) {
+        case 1: hipLaunchKernelGGL((gemm_w8_rows_kernel<1, GATED>), grid, dim3(NT), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((gemm_w8_rows_kernel<2, GATED>), grid, dim3(NT), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((gemm_w8_rows_kernel<3, GATED>), grid, dim3(NT), 0, st, a); break;
+        default: hipLaunchKernelGGL((gemm_w8_rows_kernel<4, GATED>), grid, dim3(NT), 0, st, a); break;
+    }
+}
+
+int w8_reduce(const W8Args& a, hipStream_t st, const char* what) {
+    const dim3 grid((unsigned)cdiv64((int64_t)a.M * a.N, NT));
+    if (a.R) hipLaunchKernelGGL(gemv_w8_reduce_kernel<true>, grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL(gemv_w8_reduce_kernel<false>, grid, dim3(NT), 0, st, a);
+    OTTER_CHECK_LAUNCH(what);
+    return OTTER_OK;
+}
+
+int gemv_w8_run(const W8Call& c, const char* what, const char* what_reduce) {
+    const int rc = w8_check(c, what, 16);
+    if (rc != OTTER_OK) return rc;
+    const int64_t N = c.N, K = c.K;
+    const int R = N >= 16384 ? 2 : 1;
+    const int64_t base = cdiv64(N, 16 * R);
+    int S = 1;
+    while (base * S < WG_TARGET && S < MAX_SPLIT && K / (2 * S) >= MIN_K_PER_WG) S *= 2;
+    OTTER_REQUIRE(S <= 65535, "%s: internal split", what);
+
+    W8Args a = w8_args(c);
+    a.S = S;
+    a.T = (int)cdiv64(K, KSTEP);
+    a.q = (int)cdiv64(a.T, (int64_t)S * WAVES);
+    hipStream_t st = (hipStream_t)c.stream;
+    const dim3 grid((unsigned)base, (unsigned)S);
+    if (c.gated) launch_gemv<true>(R, grid, st, a);
+    else launch_gemv<false>(R, grid, st, a);
+    OTTER_CHECK_LAUNCH(what);
+    return S > 1 ? w8_reduce(a, st, what_reduce) : OTTER_OK;
+}
+
+int gemm_w8_rows_run(const W8Call& c, const char* what, const char* what_reduce) {
+    const int rc = w8_check(c, what, ROWS_MAX_M);
+    if (rc != OTTER_OK) return rc;
+    const int64_t N = c.N, K = c.K;
+    // the split is a function of (N, K) only -- never of M -- so that a row's summation order does not depend on what it is batched with
+    const int64_t base = cdiv64(N, ROWS_BN);
+    int S = 1;
+    while (base * S <= ROWS_WG_TARGET && S < ROWS_MAX_SPLIT && K / (2 * S) >= ROWS_MIN_K_PER_WG) S *= 2;
+    OTTER_REQUIRE(base <= 0x7fffffff, "%s: internal grid", what);
+
+    W8Args a = w8_args(c);
+    a.S = S;
+    a.T = (int)cdiv64(K, ROWS_KC);
+    a.q = (int)cdiv64(a.T, S);
+    hipStream_t st = (hipStream_t)c.stream;
+    const dim3 grid((unsigned)base, (unsigned)S);
+    if (c.gated) launch_rows<true>((int)cdiv64(c.M, 16), grid, st, a);
+    else launch_rows<false>((int)cdiv64(c.M, 16), grid, st, a);
+    OTTER_CHECK_LAUNCH(what);
+    return S > 1 ? w8_reduce(a, st, what_reduce) : OTTER_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype, void* y,
                   int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes, void* stream) {
-    OTTER_REQUIRE(x && qweight && scale && y && workspace, "gemv_w8: null pointer");
-    OTTER_REQUIRE(M >= 1 && M <= 16, "gemv_w8: M=%d outside [1, 16]", (int)M);
-    OTTER_REQUIRE(N >= 1 && N <= (int64_t)1 << 30, "gemv_w8: N=%ld outside [1, 2^30]", (long)N);
-    OTTER_REQUIRE(K >= 16 && K % 16 == 0 && K <= (int64_t)1 << 30, "gemv_w8: K=%d must be a positive multiple of 16", (int)K);
-    OTTER_REQUIRE(ldw % 16 == 0 && ldx % 8 == 0 && (((uintptr_t)x | (uintptr_t)qweight | (uintptr_t)y) & 15) == 0,
-                  "gemv_w8: alignment (x, qweight, y 16-byte aligned; ldw %% 16 == 0; ldx %% 8 == 0)");
-    OTTER_REQUIRE(ldw >= K && ldx >= K && ldy >= N, "gemv_w8: a leading dimension is smaller than the row it holds");
-    OTTER_REQUIRE((y_dtype == OTTER_F32 || y_dtype == OTTER_BF16) && (!bias || bias_dtype == OTTER_F32 || bias_dtype == OTTER_BF16),
-                  "gemv_w8: y / bias dtype must be OTTER_F32 or OTTER_BF16");
-    OTTER_REQUIRE(act == 0 || act == 1 || act == 3, "gemv_w8: act=%d (0 none, 1 GELU, 3 squared ReLU)", act);
-    const int64_t need = OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K);
-    OTTER_REQUIRE(workspace_bytes >= need, "gemv_w8: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
-
-    const int R = N >= 16384 ? 2 : 1;
-    const int64_t base = cdiv64(N, 16 * R);
-    int S = 1;
-    while (base * S < WG_TARGET && S < MAX_SPLIT && K / (2 * S) >= MIN_K_PER_WG) S *= 2;
-    OTTER_REQUIRE(S <= 65535, "gemv_w8: internal split");
-
-    W8Args a;
-    a.x = (const bf16_t*)x; a.ldx = ldx;
-    a.w = (const int8_t*)qweight; a.ldw = ldw;
-    a.scale = scale; a.bias = bias; a.bias_dtype = bias_dtype;
-    a.y = y; a.ldy = ldy; a.y_dtype = y_dtype;
-    a.part = (float*)workspace;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.act = act; a.S = S;
-    a.T = (int)cdiv64(K, KSTEP);
-    a.q = (int)cdiv64(a.T, (int64_t)S * WAVES);
-    hipStream_t st = (hipStream_t)stream;
-    if (R == 2) hipLaunchKernelGGL(gemv_w8_kernel<2>, dim3((unsigned)base, (unsigned)S), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL(gemv_w8_kernel<1>, dim3((unsigned)base, (unsigned)S), dim3(NT), 0, st, a);
-    OTTER_CHECK_LAUNCH("gemv_w8");
-    if (S > 1) {
-        hipLaunchKernelGGL(gemv_w8_reduce_kernel, dim3((unsigned)cdiv64(M * N, NT)), dim3(NT), 0, st, a);
-        OTTER_CHECK_LAUNCH("gemv_w8 (reduce)");
-    }
-    return OTTER_OK;
+    return gemv_w8_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, act, workspace, workspace_bytes, stream, false,
+                        nullptr, nullptr, 0, OTTER_F32},
+                       "gemv_w8", "gemv_w8 (reduce)");
 }
 
 int otter_gemm_w8_rows(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype,
                        void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes,
                        void* stream) {
-    OTTER_REQUIRE(x && qweight && scale && y && workspace, "gemm_w8_rows: null pointer");
-    OTTER_REQUIRE(M >= 1 && M <= ROWS_MAX_M, "gemm_w8_rows: M=%d outside [1, 64]", (int)M);
-    OTTER_REQUIRE(N >= 1 && N <= (int64_t)1 << 30, "gemm_w8_rows: N=%ld outside [1, 2^30]", (long)N);
-    OTTER_REQUIRE(K >= 16 && K % 16 == 0 && K <= (int64_t)1 << 30, "gemm_w8_rows: K=%d must be a positive multiple of 16", (int)K);
-    OTTER_REQUIRE(ldw % 16 == 0 && ldx % 8 == 0 && (((uintptr_t)x | (uintptr_t)qweight | (uintptr_t)y) & 15) == 0,
-                  "gemm_w8_rows: alignment (x, qweight, y 16-byte aligned; ldw %% 16 == 0; ldx %% 8 == 0)");
-    OTTER_REQUIRE(ldw >= K && ldx >= K && ldy >= N, "gemm_w8_rows: a leading dimension is smaller than the row it holds");
-    OTTER_REQUIRE((y_dtype == OTTER_F32 || y_dtype == OTTER_BF16) && (!bias || bias_dtype == OTTER_F32 || bias_dtype == OTTER_BF16),
-                  "gemm_w8_rows: y / bias dtype must be OTTER_F32 or OTTER_BF16");
-    OTTER_REQUIRE(act == 0 || act == 1 || act == 3, "gemm_w8_rows: act=%d (0 none, 1 GELU, 3 squared ReLU)", act);
-    const int64_t need = OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES(M, N, K);
-    OTTER_REQUIRE(workspace_bytes >= need, "gemm_w8_rows: workspace of %ld bytes, %ld needed", (long)workspace_bytes, (long)need);
+    return gemm_w8_rows_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, act, workspace, workspace_bytes, stream,
+                             false, nullptr, nullptr, 0, OTTER_F32},
+                            "gemm_w8_rows", "gemm_w8_rows (reduce)");
+}
 
-    // the split is a function of (N, K) only -- never of M -- so that a row's summation order does not depend on what it is batched with
-    const int64_t base = cdiv64(N, ROWS_BN);
-    int S = 1;
-    while (base * S <= ROWS_WG_TARGET && S < ROWS_MAX_SPLIT && K / (2 * S) >= ROWS_MIN_K_PER_WG) S *= 2;
-    OTTER_REQUIRE(base <= 0x7fffffff, "gemm_w8_rows: internal grid");
+int otter_gemv_w8_gated(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype,
+                        void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, const float* gate, const void* R, int64_t ldr,
+                        int r_dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+    return gemv_w8_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, 0, workspace, workspace_bytes, stream, true,
+                        gate, R, ldr, r_dtype},
+                       "gemv_w8_gated", "gemv_w8_gated (reduce)");
+}
 
-    W8Args a;
-    a.x = (const bf16_t*)x; a.ldx = ldx;
-    a.w = (const int8_t*)qweight; a.ldw = ldw;
-    a.scale = scale; a.bias = bias; a.bias_dtype = bias_dtype;
-    a.y = y; a.ldy = ldy; a.y_dtype = y_dtype;
-    a.part = (float*)workspace;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K; a.act = act; a.S = S;
-    a.T = (int)cdiv64(K, ROWS_KC);
-    a.q = (int)cdiv64(a.T, S);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)base, (unsigned)S);
-    switch ((int)cdiv64(M, 16)) {
-        case 1: hipLaunchKernelGGL(gemm_w8_rows_kernel<1>, grid, dim3(NT), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(gemm_w8_rows_kernel<2>, grid, dim3(NT), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(gemm_w8_rows_kernel<3>, grid, dim3(NT), 0, st, a); break;
-        default: hipLaunchKernelGGL(gemm_w8_rows_kernel<4>, grid, dim3(NT), 0, st, a); break;
-    }
-    OTTER_CHECK_LAUNCH("gemm_w8_rows");
-    if (S > 1) {
-        hipLaunchKernelGGL(gemv_w8_reduce_kernel, dim3((unsigned)cdiv64(M * N, NT)), dim3(NT), 0, st, a);
-        OTTER_CHECK_LAUNCH("gemm_w8_rows (reduce)");
-    }
-    return OTTER_OK;
+int otter_gemm_w8_rows_gated(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias,
+                             int bias_dtype, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, const float* gate,
+                             const void* R, int64_t ldr, int r_dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+    return gemm_w8_rows_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, 0, workspace, workspace_bytes, stream,
+                             true, gate, R, ldr, r_dtype},
+                            "gemm_w8_rows_gated", "gemm_w8_rows_gated (reduce)");
 }
 
 int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream) {

@@ -401,6 +401,7 @@ class LlamaModel(LlamaPreTrainedModel):
 
 class LlamaForCausalLM(LlamaPreTrainedModel):
     _tied_weights_keys = None
+    accepts_last_position_only = True        # forward(..., _last_position_only=): see OtterForConditionalGeneration.generate
 
     def __init__(self, config: LlamaConfig):
         super().__init__(config)
@@ -444,10 +445,13 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
         return super()._apply(fn, *a, **k)
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, labels=None,
-                use_cache=None, return_dict=True, **unused):
+                use_cache=None, return_dict=True, _last_position_only=False, **unused):
+        """`_last_position_only` (private; generate() passes it when `lm_head` is quantised): un-embed only the last position, logits
+        [B, 1, V]."""
         out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, past_key_values=past_key_values,
                          inputs_embeds=inputs_embeds, use_cache=use_cache)
-        logits = self.lm_head(out.last_hidden_state)
+        h = out.last_hidden_state
+        logits = self.lm_head(h[:, -1:, :] if _last_position_only else h)
         loss = None
         if labels is not None:
             # HF: logits[..., :-1, :] against labels[..., 1:], mean over the valid targets (ignore_index -100)

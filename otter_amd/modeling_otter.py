@@ -218,9 +218,29 @@ class OtterGatedCrossAttentionBlock(nn.Module):
         tt = text_time
         if mode != MASK_NONE and tt is None:
             tt = ops.text_time(media_locations, attend_previous)
+        if self.ffn_is_int8():
+            return self._forward_int8_ffn(x, media, tt, mode, deferred)
         return OF.GatedCrossAttentionFn.apply(x, media, tt, mode, a.heads, a.norm.eps, a.norm.weight, a.norm.bias, a.to_q.weight,
                                               a.to_kv.weight, a.to_out.weight, self.attn_gate, ff[0].weight, ff[0].bias,
                                               ff[1].weight, ff[3].weight, self.ff_gate, deferred)
+
+    def ffn_is_int8(self) -> bool:
+        """Whether `quantize_decoder_int8(gated_blocks=True)` has replaced feed_forward[1] and [3] (otter_amd/quant.py: always both)."""
+        return not isinstance(self.feed_forward[1], nn.Linear)
+
+    def _forward_int8_ffn(self, x, media, tt, mode, deferred):
+        """forward() with an int8 FFN: the fused GatedCrossAttentionFn takes weights, so the attention half runs
+        through OF.masked_cross_attention, then its gate residual, then LayerNorm and the two Int8FrozenLinear by their own routes (GELU in
+        the first product's epilogue, the tanh-gate residual in the second's tail).  Inference only: under autograd the quantised FFN
+        raises."""
+        a, ff = self.attn, self.feed_forward
+        if deferred is not None:
+            x = x + deferred.to(x.dtype)
+        attn = OF.masked_cross_attention(x, media, tt, mode, a.heads, a.norm.eps, a.norm.weight, a.norm.bias, a.to_q.weight, a.to_kv.weight,
+                                         a.to_out.weight)
+        x1 = (attn.float() * torch.tanh(self.attn_gate.float()) + x.float()).to(x.dtype)
+        f = OF.layer_norm(x1, ff[0].weight, ff[0].bias, ff[0].eps, OF.compute_dtype_for(x))
+        return ff[3].forward_gated(ff[1](f, act="gelu"), self.ff_gate, x1)
 
     @torch.no_grad()
     def decode_step(self, x, cache, layer_index: int, deferred=None):
@@ -228,7 +248,9 @@ class OtterGatedCrossAttentionBlock(nn.Module):
         come from `cache`.  The launch sequence of GatedCrossAttentionFn.forward with the same ops and epilogues, minus the media cast, the
         `to_kv` product and the side stream they ran on, and with csrc/xattn_decode.hip in place of the 64-row-tile attention kernel:
         (add+)LayerNorm -> to_q -> xattn_decode -> to_out (scale + residual tail) -> LayerNorm -> FF up (GELU tail) -> FF down (scale +
-        residual tail).  On the CPU / in fp32 compute: the same sequence in plain torch around `MediaCache.attend_reference`."""
+        residual tail).  With an int8 FFN (`ffn_is_int8`) the two FF products are the Int8FrozenLinear's: `ff[1](f, act="gelu")` and
+        `ff[3].forward_gated(h, ff_gate, x1)`, the same two tails in the epilogues of csrc/w8.hip, still one chain of launches on one stream.
+        On the CPU / in fp32 compute: the same sequence in plain torch around `MediaCache.attend_reference`."""
         a, ff = self.attn, self.feed_forward
         N, S, D = x.shape
         if S != 1:
@@ -248,6 +270,9 @@ class OtterGatedCrossAttentionBlock(nn.Module):
             o = cache.attend(layer_index, q)
             x1 = ops.gemm_nt(o, w(a.to_out.weight, cd), out_dtype=rd, kind=OF.EPI_SCALE_RES, gate=ga, R=x2)       # attn*tanh(g)+x
             f = ops.layernorm_fwd(x1, ff[0].weight.detach(), ff[0].bias.detach(), cd, ff[0].eps, need_stats=False)[0]
+            if self.ffn_is_int8():                          # [N, 1, .] views: a one-token step, so 17 to 64 rows take the rows kernel
+                h = ff[1](f.view(N, 1, D), act="gelu")
+                return ff[3].forward_gated(h, gf, x1.view(N, 1, D))
             h = ops.gemm_nt(f, w(ff[1].weight, cd), kind=OF.EPI_GELU)
             y = ops.gemm_nt(h, w(ff[3].weight, cd), out_dtype=rd, kind=OF.EPI_SCALE_RES, gate=gf, R=x1)           # ff*tanh(g)+x1
             return y.view(N, 1, D)
@@ -259,6 +284,8 @@ class OtterGatedCrossAttentionBlock(nn.Module):
         o = cache.attend(layer_index, lin(xn, a.to_q.weight))
         x1 = (lin(o, a.to_out.weight).float() * torch.tanh(self.attn_gate.float()) + x2.float()).to(rd)
         f = F.layer_norm(x1.float(), (D,), ff[0].weight.float(), ff[0].bias.float(), ff[0].eps).to(cd)
+        if self.ffn_is_int8():
+            return ff[3].forward_gated(ff[1](f.view(N, 1, D), act="gelu"), self.ff_gate, x1.view(N, 1, D))
         y = (lin(F.gelu(lin(f, ff[1].weight)), ff[3].weight).float() * torch.tanh(self.ff_gate.float()) + x1.float()).to(rd)
         return y.view(N, 1, D)
 
@@ -531,18 +558,26 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         model.init_weights()
         return model
 
-    def quantize_decoder_int8(self) -> dict:
+    def quantize_decoder_int8(self, gated_blocks: bool = False, lm_head: bool = False) -> dict:
         """Opt-in, for generation: hold the frozen decoder's linears as int8 weights with one fp32 scale per output row
-        (otter_amd/quant.py: `quantize_frozen_decoder`), put the model in eval mode and return {"replaced", "bytes_before", "bytes_after"}.
+        (otter_amd/quant.py: `quantize_frozen_decoder`), put the model in eval mode and return {"replaced", "bytes_before", "bytes_after"}:
+        what THIS call replaced.  `gated_blocks=True` also replaces the two FFN linears of every gated cross-attention block
+        (`quantize_gated_blocks`: trainable layers, so the keyword is the statement that training is over), `lm_head=True` the un-embedding
+        (`quantize_unembedding`: an int8 copy of MPT's tied table, LLaMA's `lm_head`), of which generate() then computes only the last
+        position of the prompt pass.  A later call with more keywords quantises only what is still unquantised.
 
         This is an IN-MEMORY transformation done after loading: checkpoints stay in the reference's format.  `state_dict()` of a quantised
         model (qweight / scale buffers instead of weights) is not a reference-format checkpoint, so `save_pretrained` on it raises; the
         quantised decoder is inference-only (no autograd through it).  Calling it again replaces nothing."""
-        from .quant import quantize_frozen_decoder
+        from .quant import quantize_frozen_decoder, quantize_gated_blocks, quantize_unembedding
 
-        info = quantize_frozen_decoder(self.lang_encoder)
+        parts = [quantize_frozen_decoder(self.lang_encoder)]
+        if gated_blocks:
+            parts.append(quantize_gated_blocks(self.lang_encoder))
+        if lm_head:
+            parts.append(quantize_unembedding(self.lang_encoder))
         self.eval()
-        return info
+        return {k: sum(p[k] for p in parts) for k in ("replaced", "bytes_before", "bytes_after")}
 
     def save_pretrained(self, *args, **kwargs):
         quant = sys.modules.get(__package__ + ".quant")          # (not loaded: nothing was ever quantised)
@@ -680,6 +715,11 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         generate_kwargs.setdefault("eos_token_id", self.eoc_token_id)
         self._encode_vision_x(vision_x=vision_x)
         lm = self.lang_encoder
+        # an int8 un-embedding (quantize_decoder_int8(lm_head=True)): only the last position of a pass is un-embedded -- every caller below
+        # reads logits[:, -1] -- through the private keyword of otter_amd's own hosts
+        quant = sys.modules.get(__package__ + ".quant")
+        lkw = ({"_last_position_only": True} if quant is not None and getattr(lm, "accepts_last_position_only", False)
+               and any(isinstance(m, quant.Int8Unembedding) for m in lm.modules()) else {})
 
         def repeat_vis_x():
             for layer in lm._get_decoder_layers():
@@ -714,7 +754,7 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             past = new_static_cache(ids)
             past.share_prompt(num_beams)
             out = lm(input_ids=ids[::num_beams].contiguous(), attention_mask=mask[::num_beams].contiguous() if mask is not None else None,
-                     past_key_values=past, use_cache=True, **mkw)
+                     past_key_values=past, use_cache=True, **mkw, **lkw)
             if media[0] is not None:
                 media[0].expand(num_beams)                   # (before enable_replay and the GraphDecodeStep: `seen` is replaced)
             repeat_vis_x()                                   # the legacy cached gated block still reads vis_x per row
@@ -736,14 +776,14 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
                         past.enable_replay(mask[:, :past.length] if mask is not None else None, beams=num_beams > 1)
                         graph_step[0] = GraphDecodeStep(lm, past, media[0])
                     return graph_step[0](return_ids), past
-                out = lm(input_ids=return_ids, attention_mask=mask, past_key_values=past, use_cache=True, **mkw)
+                out = lm(input_ids=return_ids, attention_mask=mask, past_key_values=past, use_cache=True, **mkw, **lkw)
                 return out.logits[:, -1, :], past
             if use_cache and past is not None:
                 if beam_idx is not None:
                     past = [tuple(t.index_select(0, beam_idx) for t in layer) for layer in past]   # a list: the MPT host fills it in place
-                out = lm(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True, **mkw)
+                out = lm(input_ids=ids[:, -1:], attention_mask=mask, past_key_values=past, use_cache=True, **mkw, **lkw)
             else:
-                out = lm(input_ids=ids, attention_mask=mask, use_cache=use_cache, **mkw)
+                out = lm(input_ids=ids, attention_mask=mask, use_cache=use_cache, **mkw, **lkw)
             return out.logits[:, -1, :], (out.past_key_values if use_cache else None)
 
         try:

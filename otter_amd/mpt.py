@@ -79,10 +79,14 @@ def alibi_slopes(n_heads: int, alibi_bias_max: int = 8) -> torch.Tensor:
 
 
 class SharedEmbedding(nn.Embedding):
-    """mpt/custom_embedding.py:7-11."""
+    """mpt/custom_embedding.py:7-11.  `unembed_int8` (otter_amd extension, set by quant.quantize_unembedding): an int8 copy of the table that
+    the un-embedding reads in its place; the lookup keeps the table."""
 
     def forward(self, input: torch.Tensor, unembed: bool = False) -> torch.Tensor:
         if unembed:
+            q = getattr(self, "unembed_int8", None)
+            if q is not None:
+                return q(input)
             if self.weight.requires_grad and self.weight.dtype == torch.float32 and input.is_cuda and input.dtype == torch.bfloat16:
                 # trainable fp32 master (the reference unfreezes the input embeddings, modeling_otter.py:905): bf16 operand copy
                 # from the shadow cache the AdamW kernel refreshes, fp32 weight gradient straight out of the GEMM -- instead of
@@ -532,6 +536,8 @@ class MPTModel(MPTPreTrainedModel):
 
 
 class MPTForCausalLM(MPTPreTrainedModel):
+    accepts_last_position_only = True        # forward(..., _last_position_only=): see OtterForConditionalGeneration.generate
+
     def __init__(self, config: MPTConfig):
         super().__init__(config)
         self.transformer = MPTModel(config)
@@ -559,10 +565,13 @@ class MPTForCausalLM(MPTPreTrainedModel):
         self.transformer = decoder
 
     def forward(self, input_ids, past_key_values=None, attention_mask=None, labels=None, use_cache=None, return_dict=True,
-                **unused):
+                _last_position_only=False, **unused):
+        """`_last_position_only` (private; generate() passes it when the un-embedding is quantised): un-embed only the last position,
+        logits [B, 1, V]."""
         out = self.transformer(input_ids=input_ids, past_key_values=past_key_values, attention_mask=attention_mask,
                                use_cache=use_cache)
-        logits = self.transformer.wte(out.last_hidden_state, True)
+        h = out.last_hidden_state
+        logits = self.transformer.wte(h[:, -1:, :] if _last_position_only else h, True)
         if self.logit_scale is not None:
             logits = logits * self.logit_scale
         loss = None

@@ -1021,6 +1021,46 @@ def gemm_w8_rows(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfl
     return y
 
 
+def _w8_gated(name, max_rows, x, qweight, scale, gate, R, bias, out_dtype, out):
+    K.require_cuda(x, qweight, scale, gate, R, bias, out)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise K.OtterHipError(f"{name}: x must be bf16 [M, K] with a unit column stride")
+    if not _w8_weight_ok(qweight, scale):
+        raise K.OtterHipError(f"{name}: qweight int8 [N, K] (K % 16 == 0, row stride % 16 == 0, 16-B aligned), scale contiguous fp32 [N]")
+    M, Kd = x.shape
+    N = qweight.shape[0]
+    if Kd != qweight.shape[1] or not 1 <= M <= max_rows:
+        raise K.OtterHipError(f"{name}: x {tuple(x.shape)} against qweight {tuple(qweight.shape)} (1 <= M <= {max_rows})")
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        raise K.OtterHipError(f"{name}: bias must be contiguous [N]")
+    if gate is not None and (gate.dtype != torch.float32 or gate.numel() != 1):
+        raise K.OtterHipError(f"{name}: gate must be one fp32 value on the device (or None)")
+    if R is None or R.dtype not in (torch.bfloat16, torch.float32) or tuple(R.shape) != (M, N) or R.stride(1) != 1 or R.device != x.device:
+        raise K.OtterHipError(f"{name}: R must be bf16 / fp32 [M, N] with a unit column stride on x's device")
+    y = torch.empty((M, N), dtype=out_dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.device != x.device:
+        raise K.OtterHipError(f"{name}: out must be [M, N] with a unit column stride on x's device")
+    ldx, ldy, ldr = (x.stride(0), y.stride(0), R.stride(0)) if M > 1 else (Kd, N, N)      # (the row stride of a one-row view is arbitrary)
+    ws = _ws.get(8 * M * N * 4, x.device)
+    K.check(getattr(K.lib(), "otter_" + name)(x.data_ptr(), ldx, qweight.data_ptr(), qweight.stride(0), scale.data_ptr(), K.ptr(bias),
+                                              K.dt(bias) if bias is not None else K.F32, y.data_ptr(), ldy, K.dt(y), M, N, Kd, K.ptr(gate),
+                                              R.data_ptr(), ldr, K.dt(R), ws.data_ptr(), ws.numel(), K.stream()), name)
+    return y
+
+
+def gemv_w8_gated(x, qweight, scale, gate, R, bias=None, out_dtype=torch.bfloat16, out=None):
+    """y [M, N] = v * tanh(gate) + R, v = (x [M, K] . qweight [N, K]^T) * scale [N] (+ bias), in fp32 and rounded once, 1 <= M <= 16
+    (otter_gemv_w8_gated, csrc/w8.hip): the second FFN product of a gated cross-attention block with its tanh-gate residual.  gate: one fp32
+    value on the device, or None (y = v + R); R bf16 / fp32 [M, N] with a unit column stride, not overlapping y.  The rest as gemv_w8."""
+    return _w8_gated("gemv_w8_gated", GEMV_W8_MAX_ROWS, x, qweight, scale, gate, R, bias, out_dtype, out)
+
+
+def gemm_w8_rows_gated(x, qweight, scale, gate, R, bias=None, out_dtype=torch.bfloat16, out=None):
+    """gemv_w8_gated for 1 <= M <= 64 (otter_gemm_w8_rows_gated): row m of the result has the same bits whatever M is and whatever the other
+    rows of x and R hold."""
+    return _w8_gated("gemm_w8_rows_gated", GEMM_W8_ROWS_MAX_ROWS, x, qweight, scale, gate, R, bias, out_dtype, out)
+
+
 def dequant_w8(qweight, scale, out=None):
     """out [N, K] bf16 = bf16(float(qweight) * scale[:, None]) (otter_dequant_w8, csrc/w8.hip); `out`: a caller-owned bf16 [N, K] view with
     unit column stride and a row stride that is a multiple of 8."""

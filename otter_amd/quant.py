@@ -5,6 +5,10 @@ the step is a single pass over the weights.  Storing those weights as int8 with 
 moves and the decoder's footprint; the activations stay bf16 and the accumulation fp32 (csrc/w8.hip).  This is an opt-in, in-memory
 transformation applied after loading (`OtterForConditionalGeneration.quantize_decoder_int8()`); nothing on the training path changes.
 The OtterHD / Fuyu host has the same method (`FuyuForCausalLM.quantize_decoder_int8()`): `quantize_persimmon_decoder`.
+`quantize_decoder_int8(gated_blocks=True, lm_head=True)` on the MPT and LLaMA hosts adds the last weights a cached step still streams in
+bf16: the two FFN linears of every gated cross-attention block (`quantize_gated_blocks`; the second product
+carries the block's tanh-gate residual in its tail, `Int8FrozenLinear.forward_gated`) and the un-embedding (`quantize_unembedding`,
+`Int8Unembedding`).
 
 Format.  For a weight W [N, K] read as fp32:
     amax[n]  = max_k |W[n, k]|
@@ -98,6 +102,7 @@ class Int8FrozenLinear(nn.Module):
       * CPU input: F.linear(x, dequantize_weight_int8(...), bias).  The ONE deliberate exception to this package's "no CPU fallback"
         rule: the host contract (module swap, parity with the fake-quantised model, error paths) has to be testable without a GPU.  No
         product path runs the decoder on the CPU.
+    forward_gated(x, gate, residual) -- the same product with the tanh-gate residual tail of a gated cross-attention block, by the same routes.
     """
 
     def __init__(self, qweight: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None):
@@ -162,6 +167,39 @@ class Int8FrozenLinear(nn.Module):
         return (y if cd == torch.bfloat16 else y.to(cd)).view(lead + (self.out_features,))
 
 
+    def forward_gated(self, x: torch.Tensor, gate: Optional[torch.Tensor], residual: torch.Tensor) -> torch.Tensor:
+        """self(x) * tanh(gate) + residual, the tail in fp32 on the fp32 product and rounded once to residual's dtype: the second FFN
+        product of a gated cross-attention block.  `gate`: one fp32 value (None: 1), `residual`: x's leading
+        dimensions x out_features.  The routes are `forward`'s: "gemv" / "rows" run `ops.gemv_w8_gated` / `ops.gemm_w8_rows_gated`,
+        "dequant" the library GEMM of the unquantised block with its EPI_SCALE_RES tail on the dequantised weight, the CPU plain torch."""
+        if torch.is_grad_enabled() and (x.requires_grad or residual.requires_grad):
+            raise RuntimeError("the int8 decoder is inference-only: its input requires grad (run it under torch.no_grad(); training or LoRA "
+                               "on quantised weights is not supported)")
+        lead, rd = x.shape[:-1], residual.dtype
+        if tuple(residual.shape) != tuple(lead) + (self.out_features,):
+            raise ValueError("Int8FrozenLinear.forward_gated: residual %s against an output of %s" % (tuple(residual.shape), tuple(lead) + (self.out_features,)))
+        if gate is not None:
+            gate = gate.detach().reshape(1)
+        if not x.is_cuda:
+            v = F.linear(x, dequantize_weight_int8(self.qweight, self.scale, x.dtype), None if self.bias is None else self.bias.to(x.dtype))
+            return (v.float() * (torch.tanh(gate.float()) if gate is not None else 1.0) + residual.float()).to(rd)
+        x2, r2 = x.reshape(-1, self.in_features), residual.reshape(-1, self.out_features)
+        xb = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
+        how = route(xb.shape[0], x.dim() >= 3 and x.shape[-2] == 1)
+        if r2.stride(1) != 1 or r2.dtype not in (torch.bfloat16, torch.float32):
+            r2 = r2.contiguous() if r2.dtype in (torch.bfloat16, torch.float32) else r2.float()
+        if how != "dequant":
+            if xb.stride(1) != 1 or (xb.shape[0] > 1 and xb.stride(0) % 8) or xb.data_ptr() % 16:
+                xb = xb.contiguous()
+            product = ops.gemv_w8_gated if how == "gemv" else ops.gemm_w8_rows_gated
+            return product(xb, self.qweight, self.scale, gate, r2, self.bias, out_dtype=rd).view(residual.shape)
+        if self.bias is not None:
+            raise NotImplementedError("Int8FrozenLinear.forward_gated: a bias on the dequantising route (the gated blocks have none)")
+        n, k = self.qweight.shape
+        w = ops.dequant_w8(self.qweight, self.scale, out=_dequant_scratch(n * k, x.device)[: n * k].view(n, k))
+        return ops.gemm_nt(xb, w, out_dtype=rd, kind=OF.EPI_SCALE_RES, gate=gate, R=r2).view(residual.shape)
+
+
 def _decoder_layers(lang_encoder: nn.Module):
     if hasattr(lang_encoder, "_get_decoder_layers"):
         return list(lang_encoder._get_decoder_layers())
@@ -179,7 +217,8 @@ def _decoder_layers(lang_encoder: nn.Module):
 def quantize_frozen_decoder(lang_encoder: nn.Module) -> dict:
     """Replace every frozen FrozenAwareLinear inside the decoder layers (MPT: Wqkv, out_proj, up_proj, down_proj; LLaMA: q/k/v/o_proj,
     gate/up/down_proj) by an Int8FrozenLinear.  Left alone: LoRA-wrapped layers, anything trainable, the embedding / tied un-embedding and
-    lm_head, the gated cross-attention blocks (and the perceiver and CLIP, which are not part of the language model).  The compute-dtype and
+    lm_head, the gated cross-attention blocks (those two are `quantize_unembedding` and `quantize_gated_blocks`, behind keywords of their
+    own) and the perceiver and CLIP, which are not part of the language model.  The compute-dtype and
     transposed copies of what is replaced are released.  Returns {"replaced", "bytes_before", "bytes_after"}; a second call replaces nothing."""
     from .lora import LoraLinear
     from .mpt import FrozenAwareLinear
@@ -211,6 +250,96 @@ def quantize_frozen_decoder(lang_encoder: nn.Module) -> dict:
     return {"replaced": replaced, "bytes_before": before, "bytes_after": after}
 
 
+class _Tally:
+    """What one quantising call replaced: the {"replaced", "bytes_before", "bytes_after"} every such call returns."""
+
+    def __init__(self):
+        self.replaced, self.before, self.after = 0, 0, 0
+
+    def add(self, weight: torch.Tensor, bias: Optional[torch.Tensor], new: "Int8FrozenLinear") -> None:
+        self.replaced += 1
+        self.before += weight.numel() * weight.element_size() + (bias.numel() * bias.element_size() if bias is not None else 0)
+        self.after += new.nbytes()
+
+    def info(self) -> dict:
+        return {"replaced": self.replaced, "bytes_before": self.before, "bytes_after": self.after}
+
+
+def _release_shadows(weight: torch.Tensor) -> None:
+    for store in (OF.shadows._w, OF.shadows._wt):               # the compute-dtype copies a training run left of the replaced weight
+        for key in [k for k in store if k[0] == id(weight)]:
+            del store[key]
+
+
+def _swap_linear(parent: nn.Module, name: str, tally: _Tally, cls=None) -> None:
+    """Replace the plain nn.Linear `parent.name` (in_features % 16 == 0) by an Int8FrozenLinear (or the subclass `cls`), whatever its
+    requires_grad is: through `quantize_weight_int8` and the constructor, since `from_linear` refuses trainable layers."""
+    child = getattr(parent, name)
+    if type(child) is not nn.Linear or child.in_features % 16:
+        return
+    q, s = quantize_weight_int8(child.weight)
+    new = (cls or Int8FrozenLinear)(q, s, None if child.bias is None else child.bias.detach())
+    tally.add(child.weight, child.bias, new)
+    _release_shadows(child.weight)
+    setattr(parent, name, new)
+
+
+def quantize_gated_blocks(lang_encoder: nn.Module) -> dict:
+    """Replace `feed_forward[1]` and `feed_forward[3]` of every OtterGatedCrossAttentionBlock of the decoder by an Int8FrozenLinear
+    (DESIGN.md section 4.21).  These are trainable nn.Linear: as on the OtterHD host the call is the user's statement that training is over.
+    Left alone: `attn.to_q` / `to_kv` / `to_out`, both LayerNorms, both gates.  Returns the usual dict; a second call replaces nothing."""
+    tally = _Tally()
+    for layer in _decoder_layers(lang_encoder):
+        block = getattr(layer, "gated_cross_attn_layer", None)
+        ff = getattr(block, "feed_forward", None)
+        if ff is not None and all(type(ff[i]) is nn.Linear and ff[i].in_features % 16 == 0 for i in (1, 3)):     # both or neither
+            _swap_linear(block.feed_forward, "1", tally)
+            _swap_linear(block.feed_forward, "3", tally)
+    return tally.info()
+
+
+class Int8Unembedding(Int8FrozenLinear):
+    """The un-embedding (MPT: an int8 copy of the tied table, LLaMA: `lm_head`) as an Int8FrozenLinear that never dequantises: on the GPU
+    at most 16 rows run `ops.gemv_w8`, more run `ops.gemm_w8_rows` in slices of at most 64 rows (the rows of that kernel do not depend on
+    each other), so a pass of any size leaves the shared dequantisation scratch at the largest decoder weight.  generate() sends only the
+    last position of the prompt pass here."""
+
+    def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
+        if not x.is_cuda or act is not None or x.numel() // self.in_features <= GEMV_MAX_ROWS:
+            return super().forward(x, act)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return super().forward(x, act)                      # (raises: inference-only)
+        x2 = x.reshape(-1, self.in_features)
+        xb = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
+        if xb.stride(1) != 1 or xb.stride(0) % 8 or xb.data_ptr() % 16:
+            xb = xb.contiguous()
+        y = torch.empty((xb.shape[0], self.out_features), dtype=OF.compute_dtype_for(x), device=x.device)
+        for r in range(0, xb.shape[0], ROWS_MAX_ROWS):
+            ops.gemm_w8_rows(xb[r:r + ROWS_MAX_ROWS], self.qweight, self.scale, self.bias, 0, out=y[r:r + ROWS_MAX_ROWS])
+        return y.view(x.shape[:-1] + (self.out_features,))
+
+
+def quantize_unembedding(lang_encoder: nn.Module) -> dict:
+    """MPT: give the tied table `transformer.wte` an int8 copy, `wte.unembed_int8`, which `SharedEmbedding.forward(unembed=True)` then uses;
+    the table itself stays for the lookup (so the model grows by the copy while a step reads half the bytes: "bytes_before" is what the
+    un-embedding read before).  LLaMA: replace `lm_head`; a table it is tied to stays with `embed_tokens` in the same way.  Returns the
+    usual dict; a second call replaces nothing."""
+    from .mpt import SharedEmbedding
+
+    tally = _Tally()
+    wte = next((m for m in lang_encoder.modules() if isinstance(m, SharedEmbedding)), None)
+    if wte is not None:
+        if getattr(wte, "unembed_int8", None) is None and wte.weight.shape[1] % 16 == 0:
+            wte.unembed_int8 = Int8Unembedding(*quantize_weight_int8(wte.weight))
+            tally.add(wte.weight, None, wte.unembed_int8)
+        return tally.info()
+    owner = next((m for m in lang_encoder.modules() if isinstance(getattr(m, "lm_head", None), nn.Module)), None)
+    if owner is None:
+        raise ValueError("quantize_unembedding: neither a tied table nor an lm_head in %s" % lang_encoder.__class__.__name__)
+    _swap_linear(owner, "lm_head", tally, Int8Unembedding)
+    return tally.info()
+
+
 def quantize_persimmon_decoder(lm: nn.Module, lm_head: bool = True) -> dict:
     """Replace `query_key_value`, `dense`, `dense_h_to_4h` and `dense_4h_to_h` of every PersimmonDecoderLayer of `lm` (a
     fuyu.PersimmonForCausalLM) by an Int8FrozenLinear, and with `lm_head` the untied un-embedding too.  Left alone: `embed_tokens`, every
@@ -220,23 +349,8 @@ def quantize_persimmon_decoder(lm: nn.Module, lm_head: bool = True) -> dict:
     `quantize_weight_int8` and the constructor).  Returns {"replaced", "bytes_before", "bytes_after"}; a second call replaces nothing."""
     from .fuyu import PersimmonDecoderLayer
 
-    replaced, before, after = 0, 0, 0
-
-    def swap(parent, name):
-        nonlocal replaced, before, after
-        child = getattr(parent, name)
-        if type(child) is not nn.Linear or child.in_features % 16:
-            return
-        q, s = quantize_weight_int8(child.weight)
-        new = Int8FrozenLinear(q, s, None if child.bias is None else child.bias.detach())
-        before += child.weight.numel() * child.weight.element_size()
-        before += child.bias.numel() * child.bias.element_size() if child.bias is not None else 0
-        after += new.nbytes()
-        for store in (OF.shadows._w, OF.shadows._wt):           # the compute-dtype copies a training run left of the replaced weight
-            for key in [k for k in store if k[0] == id(child.weight)]:
-                del store[key]
-        setattr(parent, name, new)
-        replaced += 1
+    tally = _Tally()
+    swap = lambda parent, name: _swap_linear(parent, name, tally)
 
     for layer in list(lm.modules()):
         if isinstance(layer, PersimmonDecoderLayer):
@@ -246,4 +360,4 @@ def quantize_persimmon_decoder(lm: nn.Module, lm_head: bool = True) -> dict:
             swap(layer.mlp, "dense_4h_to_h")
     if lm_head:
         swap(lm, "lm_head")
-    return {"replaced": replaced, "bytes_before": before, "bytes_after": after}
+    return tally.info()
