@@ -281,6 +281,12 @@ typedef struct otter_flash_desc {
 } otter_flash_desc;
 
 int otter_flash_attn_fwd(const otter_flash_desc* d, void* stream);
+/* the same forward with O UNROUNDED: o32 fp32 [B, Sq, H, 128] contiguous, 16-byte aligned, takes what d->o would take before its rounding to
+ * bf16; d->o is not written (it must still be a valid aligned pointer: o32 itself will do) and lse is written as always.  head_dim 128 on
+ * the default LDS-DMA forward only (flash variant not 1 or 6).  The probabilities enter the second product as a bf16 hi + lo pair (two MFMAs per
+ * V fragment), so o32 is within a few 1e-6 of fp64 where the bf16-probability forward is within a few 1e-3: a consumer that goes on computing
+ * with O -- otter_branch_attn_merge -- then rounds once, at its own output, and has the error of a one-kernel attention */
+int otter_flash_attn_fwd_f32(const otter_flash_desc* d, float* o32, void* stream);
 /* tuning / A-B hook: 0 = default (LDS-DMA tiles, longest-first block order under the causal mask, delta inside the dQ kernel, one persistent
  * dK/dV workgroup per (batch, head) when those fill the chip evenly), 1 = register-staged tiles (v1), 2 = LDS-DMA tiles on the plain 3-D grid,
  * 3 / 5 = 2 / 0 with dK+dV at two workgroups per CU, 4 = 0 with the separate delta launch, 6 = 0 with forward version 3 (16 queries per
@@ -585,7 +591,32 @@ int otter_decode_attn_cached_shared_i8_dyn(const void* q, int64_t q_row_stride, 
                                            void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * otter_xattn_decode -- the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
+ * otter_branch_attn_merge -- the self-attention of candidate rows over a cached prompt (csrc/branch_attn.hip;
+ * StaticKVCache.attend_branches), head_dim 128, as many key heads as query heads.  N = B * C * T one-token rows, row
+ * n = (b C + c) T + t: position t (0 <= t < T <= OTTER_BRANCH_ATTN_MAX_T) of candidate c of sentence b.  Row (b, c, t) attends over
+ * the prompt of sentence b -- that part is given: o1, lse1 -- and over the keys (b, c, 0..t) of its own candidate.
+ *   q / k_new / v_new  bf16 [N, H, 128] given by row and head strides (elements, multiples of 8, not negative; dim stride 1),
+ *                      16-byte aligned: the three slices of the projection output, read in place (LLaMA: q, k rotated already).
+ *   o1     fp32 [N, H, 128] contiguous: the attention output of each row over the prompt's keys alone, unrounded (otter_flash_attn_fwd_f32).
+ *   lse1   fp32 [N / rows_per_sentence, H, rows_per_sentence] (natural log): the log-sum-exp of those scores, with the ALiBi origin
+ *          at the prompt's LAST key -- exactly what otter_flash_attn_fwd_f32 (causal = 0) writes for q viewed as
+ *          [B, rows_per_sentence, H, 128] against the prompt's keys.  -inf: no visible prompt key; o1 of that (row, head) is not read.
+ *   rows_per_sentence  C * T: a multiple of T that divides N.
+ *   alibi_slopes  fp32 [H] or NULL.      o  bf16 [N, H, 128] contiguous.
+ * With a = slopes ? slopes[h] : 0:  L1 = lse1 - a (t + 1);  e_u = scale q . k_new[(b,c,u)] + a (u - t), u = 0..t;
+ * M = max(L1, max_u e_u);  o = (exp(L1 - M) o1 + sum_u exp(e_u - M) v_new[(b,c,u)]) / (exp(L1 - M) + sum_u exp(e_u - M)), in fp32,
+ * rounded once.  Nothing but o is written; no workspace, no atomics; two calls on the same inputs give the same bits.  A bad
+ * argument (null pointer, head_dim != 128, T outside [1, 64], N not a multiple of T, rows_per_sentence, alignment, strides)
+ * launches nothing: OTTER_ERR_ARG and otter_last_error().
+ * ------------------------------------------------------------------------------------------------------- */
+#define OTTER_BRANCH_ATTN_MAX_T 64
+int otter_branch_attn_merge(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_new, int64_t k_new_row_stride,
+                            int64_t k_new_head_stride, const void* v_new, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                            const float* o1, const float* lse1, const float* alibi_slopes, void* o, int64_t N, int64_t H, int64_t T,
+                            int64_t rows_per_sentence, int64_t head_dim, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * otter_xattn_decode --the masked cross-attention core of one cached decode step over a media cache (otter_amd/media_cache.py),
  * head_dim 64: N rows (batch x beams) of ONE query each attend over the projected media of their sentence.
  *   q        bf16 [N, H * 64] with a row stride (elements, a multiple of 8, >= H * 64), 16-byte aligned.
  *   k / v    bf16 views [sentences, M, H * 64] of one buffer with a shared row stride (a multiple of 8, >= H * 64; the sentence stride

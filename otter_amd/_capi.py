@@ -128,6 +128,7 @@ SIGNATURES = {
     "otter_add_frame_embs": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _vp]),
     "otter_add_rows": (_int, [_vp, _vp, RowMap, _i64, _i64, _int, _vp]),
     "otter_flash_attn_fwd": (_int, [C.POINTER(FlashDesc), _vp]),
+    "otter_flash_attn_fwd_f32": (_int, [C.POINTER(FlashDesc), _vp, _vp]),
     "otter_flash_attn_bwd": (_int, [C.POINTER(FlashDesc), _vp]),
     "otter_flash_set_variant": (_int, [_int]),
     "otter_decode_attn": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64,
@@ -159,6 +160,8 @@ SIGNATURES = {
     "otter_decode_attn_cached_shared_i8_dyn": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
                                                       _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
                                                       _vp, _i64, _i64, _f32, _i64, _i64, _vp]),
+    "otter_branch_attn_merge": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32,
+                                       _vp]),
     "otter_xattn_decode": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _f32, _vp]),
     "otter_gemv_w8": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
     "otter_gemm_w8_rows": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),

@@ -65,6 +65,8 @@ struct FlashArgs {
     int lpt_group;         // heads (PAIR: head pairs) per group of the longest-first block order (divides the number of (b, head) blocks)
     int pair;              // head_dim 64: two heads per workgroup (the PAIR instantiations)
     int fuse_delta;        // round 4: the dQ kernel computes delta = rowsum(dO . O) and the log2 LSE itself and publishes them for dK/dV (no flash_delta launch)
+    float* o32;            // otter_flash_attn_fwd_f32 only (the O32 instances of flash_fwd2_kernel): O as fp32 [B, Sq, H, 128] contiguous; last, so that
+                           // every other kernel finds its arguments where they were
 };
 
 // In-kernel timeline of workgroup (3,0,0) / wave 0 of the forward (diagnostics build only: -DOTTER_FLASH_TIMING)
@@ -161,6 +163,16 @@ __device__ __forceinline__ void store_dt(bf16_t* rowp, const f32x16_t (&acc)[4],
             w.y = pack2bf(acc[db][4 * g + 2] * mul, acc[db][4 * g + 3] * mul);
             *reinterpret_cast<uint2*>(rowp + 32 * db + 8 * g + 4 * h2) = w;
         }
+}
+
+// the same registers as fp32, unrounded (otter_flash_attn_fwd_f32): 16 bytes per r-group
+__device__ __forceinline__ void store_dt_f32(float* rowp, const f32x16_t (&acc)[4], float mul, int h2) {
+#pragma unroll
+    for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(rowp + 32 * db + 8 * g + 4 * h2) =
+                make_float4(acc[db][4 * g + 0] * mul, acc[db][4 * g + 1] * mul, acc[db][4 * g + 2] * mul, acc[db][4 * g + 3] * mul);
 }
 
 // head-pair form (see "head pairs" below): d blocks 0-1 belong to the first head of the pair (scaled by mul0), blocks 2-3 to the second
@@ -441,8 +453,10 @@ __device__ __forceinline__ void flash_dma_tile(u32x4_t rk, u32x4_t rv, char* kds
 // score).  Separate interior / masked paths as in the 128-wide kernels did not fit the 256 registers of two workgroups per CU (84-392 B of
 // scratch per lane, reloaded through VMEM in front of every tile) and measured slower, as did one workgroup per CU with 512 registers
 // (C5 shape, forward / backward: 142 / 451 us one path, 153 / 650 two paths, 196 / 505 one workgroup per CU; zero-padded heads 205 / 694).
-template <bool LPT, bool PAIR = false, bool ALIBI = true>   // ALIBI = false (pair kernels only): no slopes, the bias arithmetic is compiled out
+// O32 (128-wide heads only; otter_flash_attn_fwd_f32): O leaves unrounded, as fp32 rows of a.o32, and P enters P V as a bf16 hi + lo pair; a.o is not written
+template <bool LPT, bool PAIR = false, bool ALIBI = true, bool O32 = false>   // ALIBI = false (pair kernels only): no slopes, the bias arithmetic is compiled out
 __global__ __launch_bounds__(256, 2) void flash_fwd2_kernel(FlashArgs a) {
+    static_assert(!(O32 && PAIR), "flash_fwd2_kernel: fp32 output for 128-wide heads only");
     BLK_BEGIN(0);
     extern __shared__ __attribute__((aligned(16))) char smem[];  // K0 | K1 | V0 | V1, 16 KB each
     const int tid = threadIdx.x, lane = tid & 63, h2 = lane >> 5, ql = lane & 31;
@@ -713,6 +727,13 @@ __global__ __launch_bounds__(256, 2) void flash_fwd2_kernel(FlashArgs a) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const bf16x8_t pf = pack8(s[kbk], 8 * c);
+                // O32: the probabilities enter the product as bf16(p) + bf16(p - bf16(p)), two MFMAs per V fragment: P V to ~2^-17 relative
+                // instead of 2^-9, so that the fp32 O is worth its bits (the other instances: one MFMA, as ever)
+                bf16x8_t pl;
+                if constexpr (O32) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pl[j] = (__bf16)(s[kbk][8 * c + j] - (float)pf[j]);
+                }
 #pragma unroll
                 for (int db = 0; db < 4; ++db) {
                     const char* tp = Vc + (vto ^ (db << 6)) + (32 * kbk + 16 * c) * 256;
@@ -720,6 +741,7 @@ __global__ __launch_bounds__(256, 2) void flash_fwd2_kernel(FlashArgs a) {
                     const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(tp + 2048));
                     const s16x8_t vfr = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                     o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vfr), pf, o[db], 0, 0, 0);
+                    if constexpr (O32) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vfr), pl, o[db], 0, 0, 0);
                 }
             }
         FPRIO(1, 0);
@@ -749,6 +771,13 @@ __global__ __launch_bounds__(256, 2) void flash_fwd2_kernel(FlashArgs a) {
             }
         }
 #endif
+        return;
+    }
+    if constexpr (O32) {
+        if (qi < a.Sq) {
+            store_dt_f32(a.o32 + (((int64_t)b * a.Sq + qi) * a.H + hd) * 128, o, inv, h2);
+            if (h2 == 0) a.lse[((int64_t)b * a.H + hd) * a.Sq + qi] = lsum > 0.f ? m * LN2 + logf(lsum) : -INFINITY;
+        }
         return;
     }
 #if OTTER_FLASH_ROWSTORE
@@ -2181,6 +2210,26 @@ int otter_flash_attn_fwd(const otter_flash_desc* d, void* stream) {
         hipLaunchKernelGGL(flash_fwd_kernel, dim3((a.Sq + 127) / 128, a.H, a.B), dim3(256), smem, (hipStream_t)stream, a);
     }
     OTTER_CHECK_LAUNCH("flash_fwd");
+    return OTTER_OK;
+}
+
+int otter_flash_attn_fwd_f32(const otter_flash_desc* d, float* o32, void* stream) {
+    FlashArgs a;
+    int rc = fill_args(d, a, false);
+    if (rc) return rc;
+    OTTER_REQUIRE(o32 && ((uintptr_t)o32 & 15) == 0, "flash_fwd_f32: o32 must be given, 16-byte aligned");
+    OTTER_REQUIRE(!a.pair, "flash_fwd_f32: head_dim 128 only");
+    OTTER_REQUIRE(g_flash_variant != 1 && g_flash_variant != 6 && (int64_t)a.Sk * a.ks.s * 2 < (int64_t(1) << 31) &&
+                      (int64_t)a.Sk * a.vs.s * 2 < (int64_t(1) << 31),
+                  "flash_fwd_f32: only the default LDS-DMA forward writes fp32 (variant not 1 or 6, K / V panels under 2 GB)");
+    a.o32 = o32;
+    const int smem = 65536 + KMASK_TILES * 8;
+    static bool once = false;
+    if (!once) { rc = set_smem(flash_fwd2_kernel<false, false, true, true>, smem); if (rc) return rc; once = true; }
+    // the plain 3-D grid, causal or not (the longest-first order is a matter of the causal training launches)
+    hipLaunchKernelGGL((flash_fwd2_kernel<false, false, true, true>), dim3((unsigned)((a.Sq + 127) / 128), a.H, a.B), dim3(256), smem,
+                       (hipStream_t)stream, a);
+    OTTER_CHECK_LAUNCH("flash_fwd_f32");
     return OTTER_OK;
 }
 

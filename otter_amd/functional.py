@@ -830,6 +830,29 @@ def cross_entropy_bf16(logits2d, labels):
     return CrossEntropyBf16Fn.apply(logits2d, labels)
 
 
+@torch.no_grad()
+def token_logprobs(logits2d, labels):
+    """log_softmax(logits [rows, V])[r, labels[r, k]] as fp32 [rows, K] for int64 labels [rows, K]; 0 for a negative label.  No autograd, no
+    reduction.  On the GPU in bf16 with V % 4 == 0 (the conditions under which the hosts' loss takes it) the normaliser comes from
+    csrc/loss.hip's forward, `otter_cross_entropy_fwd`, in one read of the logits: with K == 1 its per-row nll is the answer, with more
+    labels per row its lse is subtracted from the gathered logits.  Everywhere else torch's log-softmax in fp32 at least."""
+    rows, V = logits2d.shape
+    neg = labels < 0
+    if (logits2d.is_cuda and logits2d.dtype == torch.bfloat16 and V % 4 == 0 and logits2d.stride(1) == 1 and logits2d.stride(0) % 4 == 0
+            and os.environ.get("OTTER_TORCH_CE") != "1"):
+        K_ = ops.K
+        first = labels[:, 0].contiguous()
+        lse = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+        nll = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+        K_.check(K_.lib().otter_cross_entropy_fwd(logits2d.data_ptr(), logits2d.stride(0), first.data_ptr(), lse.data_ptr(), nll.data_ptr(),
+                                                  rows, V, K_.stream()), "cross_entropy_fwd")
+        if labels.shape[1] == 1:
+            return -nll.view(rows, 1)
+        return (logits2d.gather(1, labels.clamp(min=0)).float() - lse.view(rows, 1)).masked_fill(neg, 0.0)
+    lf = logits2d.double() if logits2d.dtype == torch.float64 else logits2d.float()
+    return torch.log_softmax(lf, dim=-1).gather(1, labels.clamp(min=0)).masked_fill(neg, 0.0).float()
+
+
 def masked_cross_attention(x, media, tt, mask_mode, heads, eps, norm_w, norm_b, Wq, Wkv, Wo):
     """OtterMaskedCrossAttention.forward (modeling_otter.py:262-340) used stand-alone: returns to_out(attn) in the compute
     dtype (bf16 under autocast, like the reference)."""

@@ -80,6 +80,12 @@ path through csrc/decode_cache_i8.hip; "1": the kernel below the threshold too);
 OTTER_SHARED_PREFIX=1 does not force it.  The layout and the
 allocation stay as they are: the non-leader rows' slots [0, shared_len) are allocated and never touched, so sharing saves prompt-pass work
 and key / value traffic, not cache memory.
+
+Candidate rows (`attend_branches`, `branches(C, T)`; `OtterForConditionalGeneration.score_candidates`): a filled cache of B prompts is READ by
+N = B * C * T one-token rows, row n = (b C + c) T + t the t-th teacher-forced token of candidate c of sentence b, which attends over prompt b
+and over tokens 0..t of its own candidate.  In bf16 at head_dim 128 that is the non-causal flash forward over `k[layer, :, :, :length]` in
+place plus csrc/branch_attn.hip (`ops.branch_attn_merge`), everywhere else `attend_branches_reference`.  Nothing is appended and `length`
+stays: the prompt serves any number of such passes.  A multi-token APPEND is still refused by `check_step`.
 """
 from __future__ import annotations
 
@@ -484,6 +490,102 @@ class StaticKVCache:
             o = o.masked_fill(dead[:, None, None], 0.0)
         return o.reshape(N, H * d).to(out_dtype)
 
+    # ---- candidate rows over the cached prompt (OtterForConditionalGeneration.score_candidates) -----------------------------------------------
+
+    def _check_branches(self, q, k_new, v_new, C: int, T: int, key_valid):
+        """The raises of `attend_branches` / `attend_branches_reference`; returns (B, P, N)."""
+        if self.int8:
+            raise NotImplementedError("StaticKVCache.attend_branches: an int8 key / value cache is not built for candidate rows")
+        if self.replay:
+            raise ValueError("StaticKVCache.attend_branches: the cache is in replay mode (its position belongs to a captured step)")
+        if self.group > 1 or self.src is not None:
+            raise ValueError("StaticKVCache.attend_branches: a shared-prompt cache or one with a beam table: candidate rows read row b of the "
+                             "cache as the prompt of sentence b")
+        if self.length == 0:
+            raise ValueError("StaticKVCache.attend_branches: the cache is empty (the prompt pass fills it)")
+        B, P, C, T = self.rows, self.length, int(C), int(T)
+        if C < 1 or T < 1 or T > 64:
+            raise ValueError("StaticKVCache.attend_branches: C >= 1 and 1 <= T <= 64 (got C=%d, T=%d)" % (C, T))
+        N = B * C * T
+        if q.dim() != 3 or q.shape[0] != N or q.shape[2] != self.head_dim or tuple(k_new.shape) != (N, self.n_heads, self.head_dim) \
+                or tuple(v_new.shape) != tuple(k_new.shape) or q.shape[1] % self.n_heads:
+            raise ValueError("StaticKVCache.attend_branches: q [%d, H, %d] and k_new / v_new [%d, %d, %d] for %d sentences x %d candidates x %d "
+                             "positions, got %s / %s / %s" % (N, self.head_dim, N, self.n_heads, self.head_dim, B, C, T, tuple(q.shape),
+                                                              tuple(k_new.shape), tuple(v_new.shape)))
+        if key_valid is not None and tuple(key_valid.shape) != (B, P):
+            raise ValueError("StaticKVCache.attend_branches: key_valid must be the prompt's mask [%d, %d], got %s" % (B, P, tuple(key_valid.shape)))
+        return B, P, N
+
+    def branches(self, C: int, T: int) -> "_BranchView":
+        """The cache as a host's cached-step code sees it during a branch pass: `attend` is `attend_branches` for C candidates of T positions."""
+        return _BranchView(self, C, T)
+
+    def attend_branches(self, layer: int, q, k_new, v_new, scale: float, C: int, T: int, key_valid=None, slopes=None) -> torch.Tensor:
+        """Candidate rows over the cached prompt: N = rows * C * T one-token rows, row n = (b C + c) T + t the t-th position of candidate c of
+        sentence b.  Row (b, c, t) attends over the `length` prompt keys of cache row b and over the own keys (b, c, 0..t) of k_new -- nothing
+        of another candidate.  q [N,H,d], k_new / v_new [N,H_kv,d] views of the projection output (LLaMA: q and k rotated already, at positions
+        prompt position + t); key_valid uint8 / bool [rows, length], the PROMPT's mask, or None; slopes fp32 [H] or None (ALiBi: the newest
+        key of row (b, c, t) is its own, `length + t`).  Returns o [N, H*d] in q's dtype.  Nothing is written into the cache and neither
+        `length` nor `src` changes: the prompt stays reusable for any number of such passes.
+
+        On the GPU in bf16 at head_dim 128 two launches: the non-causal flash forward of the sentence's C*T queries over the cache's own
+        `k[layer, :, :, :length]` / `v[...]`, read in place through a [rows, length, H, 128] strided view (csrc/flash.hip returns o1 in fp32 and lse1),
+        and csrc/branch_attn.hip (`ops.branch_attn_merge`), which scores the own keys and merges the two softmax pieces.  Everywhere else
+        `attend_branches_reference`."""
+        B, P, N = self._check_branches(q, k_new, v_new, C, T, key_valid)
+        if not self.uses_kernel(q, k_new.shape[1]):
+            return self.attend_branches_reference(layer, q, k_new, v_new, scale, C, T, key_valid=key_valid, slopes=slopes)
+        from . import ops
+
+        H, d, CT = q.shape[1], self.head_dim, int(C) * int(T)
+        kp, vp = self.k[layer, :, :, :P].permute(0, 2, 1, 3), self.v[layer, :, :, :P].permute(0, 2, 1, 3)    # [rows, P, H, 128] views
+        kv = key_valid.to(torch.uint8).contiguous() if key_valid is not None else None
+        q4 = q.as_strided((B, CT, H, d), (CT * q.stride(0), q.stride(0), q.stride(1), 1))
+        o1, lse1 = ops.flash_attn_fwd_f32(q4, kp, vp, slopes, kv, scale, causal=False)       # o1 unrounded: the answer is rounded once, by the merge
+        o = ops.branch_attn_merge(q, k_new, v_new, o1.view(N, H, d), lse1, scale, int(T), CT, slopes=slopes)
+        return o.view(N, H * d)
+
+    def attend_branches_reference(self, layer: int, q, k_new, v_new, scale: float, C: int, T: int, key_valid=None, slopes=None) -> torch.Tensor:
+        """The two stages of `attend_branches` in plain torch on any device and dtype, fp32 at least.  Stage 1, what the flash forward returns:
+        every row's scores over the prompt keys of its sentence, ALiBi slope * (j - (length - 1)), padding mask -> lse1 and o1 (a fully
+        masked prompt: lse1 = -inf, o1 = 0).  Stage 2, csrc/branch_attn.hip: L1 = lse1 - slope * (t + 1); own scores e_u = scale q . k_new[u]
+        + slope * (u - t) for u <= t; M = max(L1, max e_u); o = (exp(L1 - M) o1 + sum exp(e_u - M) v_new[u]) / (exp(L1 - M) + sum exp(e_u - M))."""
+        B, P, N = self._check_branches(q, k_new, v_new, C, T, key_valid)
+        C, T = int(C), int(T)
+        H, d = q.shape[1], self.head_dim
+        ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+        rep = H // k_new.shape[1]
+        grow = lambda t: t.repeat_interleave(rep, dim=1) if rep > 1 else t
+        qf = q.to(ct).view(B, C * T, H, d) * scale
+        sl = slopes.to(ct).view(1, H, 1, 1) if slopes is not None else None
+        # stage 1: the prompt
+        kp, vp = grow(self.k[layer, :, :, :P].to(ct)), grow(self.v[layer, :, :, :P].to(ct))                  # [B, H, P, d]
+        s1 = torch.einsum("bnhd,bhjd->bhnj", qf, kp)
+        if sl is not None:
+            s1 = s1 + sl * torch.arange(1 - P, 1, device=q.device, dtype=ct).view(1, 1, 1, P)
+        if key_valid is not None:
+            s1 = s1.masked_fill(~key_valid.bool().view(B, 1, 1, P), float("-inf"))
+        lse1 = torch.logsumexp(s1, dim=-1)                                                                   # [B, H, CT]; -inf: nothing visible
+        p1 = torch.exp(s1 - torch.where(torch.isinf(lse1), torch.zeros_like(lse1), lse1).unsqueeze(-1))
+        o1 = torch.einsum("bhnj,bhjd->bhnd", p1, vp)                                                         # (0 where nothing is visible)
+        # stage 2: the own keys and the merge
+        tpos = torch.arange(T, device=q.device)
+        q5 = qf.view(B, C, T, H, d)
+        k5, v5 = grow(k_new.to(ct)).view(B, C, T, H, d), grow(v_new.to(ct)).view(B, C, T, H, d)
+        e = torch.einsum("bcthd,bcuhd->bchtu", q5, k5)
+        rel = (tpos.view(1, T) - tpos.view(T, 1)).to(ct)                                                     # [t, u] = u - t
+        if sl is not None:
+            e = e + sl.view(1, 1, H, 1, 1) * rel
+        e = e.masked_fill((rel > 0).view(1, 1, 1, T, T), float("-inf"))
+        L1 = lse1.view(B, H, C, T).permute(0, 2, 1, 3)                                                       # [B, C, H, T]
+        if sl is not None:
+            L1 = L1 - sl.view(1, 1, H, 1) * (tpos + 1).to(ct).view(1, 1, 1, T)
+        M = torch.maximum(L1, e.amax(dim=-1))
+        w1, pu = torch.exp(L1 - M), torch.exp(e - M.unsqueeze(-1))
+        o1 = o1.view(B, H, C, T, d).permute(0, 2, 1, 3, 4)                                                   # [B, C, H, T, d]
+        o = (w1.unsqueeze(-1) * o1 + torch.einsum("bchtu,bcuhd->bchtd", pu, v5)) / (w1 + pu.sum(dim=-1)).unsqueeze(-1)
+        return o.permute(0, 1, 3, 2, 4).reshape(N, H * d).to(q.dtype)
+
     # ---- the cached step of the Persimmon host (OtterHD / Fuyu-8B): q / k LayerNorm per head + partial rotary fused into the step ---------
 
     def uses_persimmon_kernel(self, qkv: torch.Tensor, rot: int) -> bool:
@@ -536,3 +638,22 @@ class StaticKVCache:
         self.k[layer, :, :, pos] = kf.to(self.dtype)
         self.v[layer, :, :, pos] = v_new.to(self.dtype)
         return self._attend_appended(layer, qf, pos, scale, key_valid, None, qkv.dtype)
+
+
+class _BranchView:
+    """What a host's cached-step code gets in place of the cache during a branch pass (`StaticKVCache.branches(C, T)`): its `attend` is the
+    cache's `attend_branches` for C candidates of T positions per sentence.  Rotary embeddings are the host's business here (the rows of one
+    pass stand at T different positions): `attend` takes q and k rotated already and refuses cos / sin.  Never in replay mode."""
+    replay = False
+
+    def __init__(self, cache: StaticKVCache, C: int, T: int):
+        self.cache, self.C, self.T = cache, int(C), int(T)
+
+    @property
+    def length(self) -> int:
+        return self.cache.length
+
+    def attend(self, layer: int, q, k_new, v_new, scale: float, cos=None, sin=None, key_valid=None, slopes=None) -> torch.Tensor:
+        if cos is not None or sin is not None:
+            raise ValueError("StaticKVCache.branches: q and k_new come rotated; cos / sin must be None")
+        return self.cache.attend_branches(layer, q, k_new, v_new, scale, self.C, self.T, key_valid=key_valid, slopes=slopes)

@@ -30,7 +30,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from . import functional as OF
 from . import ops
-from .kv_cache import StaticKVCache
+from .kv_cache import StaticKVCache, _BranchView
 from .mpt import FrozenAwareLinear, _is_int8
 
 
@@ -169,6 +169,16 @@ class LlamaAttention(nn.Module):
         return (x.is_cuda and OF.compute_dtype_for(x) == torch.bfloat16 and self.head_dim == 128 and self.n_kv == self.n_heads
                 and s_past == 0 and default_positions and self._qkv.usable(x) and os.environ.get("OTTER_NO_FLASH") != "1")
 
+    @staticmethod
+    def _rotate_rows(x, cos, sin, T: int):
+        """x [N, h, d] one-token rows, row n at the position of cos / sin row n % T (fp32 [T, d]) -> rotated, contiguous.  csrc's rope
+        kernel on the GPU in bf16 (the rows read as [N / T, T, h, d]), the plain path's formula everywhere else."""
+        N, h, d = x.shape
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            return ops.rope(x.reshape(N // T, T, h, d), cos.contiguous(), sin.contiguous()).view(N, h, d)
+        c, s_ = cos.to(x.dtype).repeat(N // T, 1)[:, None], sin.to(x.dtype).repeat(N // T, 1)[:, None]
+        return x * c + _rotate_half(x) * s_
+
     def forward(self, x, cos, sin, attn_mask=None, key_valid=None, past_key_value=None, use_cache=False, flash=False, static=None):
         """x [B,S,D] (compute dtype); cos/sin fp32 [S, d] for this call's positions (or [B,S,d] with custom position_ids);
         attn_mask: additive [B or 1,1,S,Sk] for the plain path; key_valid uint8 [B,S] for the flash path."""
@@ -186,6 +196,12 @@ class LlamaAttention(nn.Module):
                 q, k, v = qkv[:, :H * d], qkv[:, H * d:(H + Hk) * d], qkv[:, (H + Hk) * d:]
             else:
                 q, k, v = self.q_proj(x)[:, 0], self.k_proj(x)[:, 0], self.v_proj(x)[:, 0]
+            if isinstance(cache, _BranchView):
+                # candidate rows (`_forward_branches`): row n stands at position prompt length + n % T, so q and k are rotated here, with
+                # the rotary op of the uncached paths on cos / sin [T, d], and the cache's branch attention takes them as they are
+                q, k = self._rotate_rows(q.view(B, H, d), cos, sin, cache.T), self._rotate_rows(k.view(B, Hk, d), cos, sin, cache.T)
+                o = cache.attend(layer, q, k, v.view(B, Hk, d), self.scale, key_valid=key_valid)
+                return self.o_proj(o.view(B, 1, H * d)), None
             if cache.replay:                                                    # the whole tables: the kernel takes row pos itself
                 c, s_ = cos, sin
             else:
@@ -335,6 +351,29 @@ class LlamaModel(LlamaPreTrainedModel):
         cache.end_step()
         return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
 
+    @torch.no_grad()
+    def _forward_branches(self, branch_ids, cache: StaticKVCache, attention_mask):
+        """Candidate rows over a filled StaticKVCache (OtterForConditionalGeneration.score_candidates): branch_ids int64 [B, C, T], the first
+        T input tokens of C candidate continuations of each of the cache's B prompts; attention_mask [B, P] the PROMPT's mask or None.  All
+        N = B*C*T tokens go through the decoder as one-token rows [N, 1, D] in one pass: every layer runs its cached-step code, with
+        `cache.attend_branches` (through `cache.branches(C, T)`) where a step has `cache.attend`.  Token t of a candidate stands at position
+        prompt length + t, padding counted, as a cached step after a left-padded prompt does (`_forward_static` with default positions).
+        Returns the final-norm hidden rows [B, C, T, D].  Nothing is appended: no `end_step`."""
+        B, C, T = branch_ids.shape
+        x = self.embed_tokens(branch_ids.reshape(B * C * T, 1))
+        P = cache.length
+        cos_t, sin_t = self.rotary_emb.tables(P + T, x.device)
+        cos, sin = cos_t[P:P + T], sin_t[P:P + T]
+        key_valid = attention_mask[:, -P:].to(torch.uint8) if attention_mask is not None else None
+        view, delta = cache.branches(C, T), None
+        for i, layer in enumerate(self.layers):
+            if delta is not None and getattr(layer, "gated_cross_attn_layer", None) is not None:
+                x = x + delta
+                delta = None
+            x, _, delta = layer(x, cos=cos, sin=sin, key_valid=key_valid, deferred=delta, defer_out=True, static=(view, i))
+        _, x = self.norm(x, delta=delta, out_dtype=OF.compute_dtype_for(x))
+        return x.view(B, C, T, -1)
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 use_cache=None, return_dict=True, **unused):
         if (input_ids is None) == (inputs_embeds is None):
@@ -443,6 +482,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel):
     def _apply(self, fn, *a, **k):
         self.release_fused_copies()
         return super()._apply(fn, *a, **k)
+
+    def _unembed(self, h):
+        """Hidden rows [..., D] -> logits [..., V] through `lm_head` (or its int8 form), as `forward` computes them: what `score_candidates`
+        un-embeds its candidate rows with."""
+        return self.lm_head(h)
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None, labels=None,
                 use_cache=None, return_dict=True, _last_position_only=False, **unused):

@@ -114,6 +114,21 @@ class MediaCache:
         self.seen = self.seen.repeat_interleave(beams)
         self.rows, self.rows_per_media = self.sentences * beams, beams
 
+    def rows_view(self, n: int) -> "MediaCache":
+        """A filled cache read for rows * n rows, row r reading the media and the <image> count of this cache's row r // n: what the candidate
+        rows of `score_candidates` attend through (n = C * T rows per sentence, none of which holds the media token, so the count IS their
+        text_time).  A new object with its own copy of the counts over the SAME projected media: this cache is not changed, may be read
+        through any number of views, and goes on as it was.  (`expand` is the mutating, one-call form beam search uses.)"""
+        n = int(n)
+        if not self.filled:
+            raise ValueError("MediaCache.rows_view: the cache is empty (the prompt pass fills it)")
+        if n < 1:
+            raise ValueError("MediaCache.rows_view: n >= 1 (got %d)" % n)
+        view = MediaCache(self.rows * n, self.media_token_id, rows_per_media=self.rows_per_media * n)
+        view.seen, view.kv = self.seen.repeat_interleave(n), self.kv
+        view.T_img, view.n, view.heads, view.mask_mode, view.filled = self.T_img, self.n, self.heads, self.mask_mode, True
+        return view
+
     def advance(self, new_ids: torch.Tensor) -> torch.Tensor:
         """One step: new_ids [rows] or [rows, 1].  Returns the step's text_time, int32 [rows] (the cache's own tensor)."""
         if not self.filled:

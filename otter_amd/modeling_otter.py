@@ -407,6 +407,35 @@ class OtterLMMixin(nn.Module):
             for layer in layers:
                 layer.condition_media_step(None)
 
+    @torch.no_grad()
+    def forward_branches(self, branch_ids, cache, media_cache, attention_mask=None):
+        """Candidate rows over a cached prompt (OtterForConditionalGeneration.score_candidates): branch_ids int64 [B, C, T], the first T input
+        tokens of C continuations of each prompt; `cache` the StaticKVCache and `media_cache` the MediaCache the prompt pass filled;
+        attention_mask the prompt's [B, P] or None.  The decoder host runs all B*C*T tokens as one-token rows (`_forward_branches` of
+        otter_amd/mpt.py and llama.py); every gated block runs its `decode_step` over a view of the media cache in which row r reads
+        sentence r // (C*T) (`MediaCache.rows_view`: neither cache is changed).  Returns the final-norm hidden rows [B, C, T, D]."""
+        decoder = self.get_decoder() if hasattr(self, "get_decoder") else None
+        if not hasattr(decoder, "_forward_branches"):
+            raise NotImplementedError("forward_branches: the decoder host %s has no branch pass (MPT and LLaMA have)" % type(self).__name__)
+        B, C, T = branch_ids.shape
+        layers = self._get_decoder_layers()
+        view = media_cache.rows_view(C * T)
+        locations = torch.zeros((B * C * T, 1), dtype=torch.bool, device=branch_ids.device)    # (no candidate row holds the media token)
+        before = [(l.media_locations, l.attend_previous, l.text_time) for l in layers]
+        try:
+            for i, layer in enumerate(layers):
+                layer.condition_media_locations(locations)
+                layer.condition_attend_previous(True)
+                layer.condition_text_time(view.seen.view(-1, 1))
+                layer.condition_media_step((view, i))
+            return decoder._forward_branches(branch_ids, cache, attention_mask)
+        finally:
+            for layer, (ml, ap, tt) in zip(layers, before):
+                layer.condition_media_step(None)
+                layer.condition_media_locations(ml)
+                layer.condition_attend_previous(ap)
+                layer.condition_text_time(tt)
+
     def is_conditioned(self) -> bool:
         return all(l.is_conditioned() for l in self._get_decoder_layers())
 
@@ -792,6 +821,98 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
             if graph_step[0] is not None:
                 graph_step[0].release()
             self.lang_encoder.clear_conditioned_layers()
+
+
+    @torch.no_grad()
+    def score_candidates(self, vision_x: torch.Tensor, lang_x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, *, candidates,
+                         candidate_mask=None, max_rows: int = 1024, return_token_logprobs: bool = False):
+        """Rank classification over a cached prompt (the reference's pipeline/benchmarks/public_datasets_suite/evaluate.py:1049-1176: encode
+        image and prompt once, teacher-force every class name over the cached prompt, rank by the product of the token probabilities).
+        `candidates`: int64 [C, T] (the same list for every sentence) or [B, C, T], right-padded, T <= 64; `candidate_mask`: bool of the same
+        shape, True on real tokens (default: all real).  Returns fp32 [B, C]: the sum over a candidate's real tokens of
+        log P(token | image, prompt, earlier tokens) -- the log of the reference's `class_prob`; with `return_token_logprobs=True` also the
+        terms, [B, C, T] (0 on padding).
+
+        One prompt pass of B rows fills a fresh StaticKVCache and MediaCache (the path of `generate(cache_implementation="static",
+        cross_attention_cache=True)`); its last-position logits give every candidate's first token.  Tokens 1..T-1 come from branch passes
+        (`forward_branches`): all positions of all candidates of a chunk go through the decoder at once as one-token rows that read the
+        shared prompt in place -- `StaticKVCache.attend_branches`, csrc/flash.hip + csrc/branch_attn.hip on the GPU in bf16.  The rows are
+        un-embedded by the host's own head (its int8 form included) and the token log-probabilities picked by csrc/loss.hip's forward.
+        Candidates are chunked so that a pass has at most `max_rows` rows (never less than one candidate per sentence); a chunk is as long
+        as its longest candidate.  `max_rows` bounds the memory of a pass (rows x vocabulary logits above all); 1024 is not a tuned figure.
+        T == 1 runs no branch pass.  The conditioning is cleared on the way out, also after an exception.
+
+        ValueError: a candidate that holds the media token (it would change the image count of the rows after it), T > 64, a candidate
+        without a real token, a mask that is not right-padded, shapes that do not fit."""
+        from .kv_cache import StaticKVCache, cache_geometry
+        from .media_cache import MediaCache
+
+        lm = self.lang_encoder
+        if not hasattr(lm, "_unembed") or not hasattr(lm, "forward_branches"):
+            raise NotImplementedError("score_candidates: the MPT and LLaMA decoder hosts only")
+        if lang_x.dim() != 2:
+            raise ValueError("score_candidates: lang_x must be [B, P], got %s" % (tuple(lang_x.shape),))
+        B, P = lang_x.shape
+        cand = torch.as_tensor(candidates)
+        if cand.dtype != torch.int64 or cand.dim() not in (2, 3):
+            raise ValueError("score_candidates: candidates must be int64 [C, T] or [B, C, T], got %s %s" % (cand.dtype, tuple(cand.shape)))
+        cmask = torch.ones_like(cand, dtype=torch.bool) if candidate_mask is None else torch.as_tensor(candidate_mask)
+        if cmask.dtype != torch.bool or tuple(cmask.shape) != tuple(cand.shape):
+            raise ValueError("score_candidates: candidate_mask must be bool of the candidates' shape %s, got %s %s"
+                             % (tuple(cand.shape), cmask.dtype, tuple(cmask.shape)))
+        if cand.dim() == 2:
+            cand, cmask = cand.unsqueeze(0).expand(B, -1, -1), cmask.unsqueeze(0).expand(B, -1, -1)
+        if cand.shape[0] != B or cand.shape[1] < 1 or cand.shape[2] < 1:
+            raise ValueError("score_candidates: candidates %s for %d sentences: [C, T] or [%d, C, T] with C, T >= 1" % (tuple(cand.shape), B, B))
+        C, T = cand.shape[1:]
+        if T > 64:
+            raise ValueError("score_candidates: T=%d: a candidate has at most 64 tokens" % T)
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, P):
+            raise ValueError("score_candidates: attention_mask must be [%d, %d], got %s" % (B, P, tuple(attention_mask.shape)))
+        max_rows = int(max_rows)
+        if max_rows < 1:
+            raise ValueError("score_candidates: max_rows >= 1 (got %d)" % max_rows)
+        cand, cmask = cand.to(lang_x.device), cmask.to(lang_x.device)
+        lengths = cmask.sum(dim=-1)                                               # [B, C]
+        if bool((lengths == 0).any()):
+            raise ValueError("score_candidates: a candidate without a real token")
+        if bool((cmask[..., 1:] & ~cmask[..., :-1]).any()):
+            raise ValueError("score_candidates: candidate_mask must be right-padded (real tokens first)")
+        vocab = self.lang_encoder.get_input_embeddings().weight.shape[0]
+        if bool((cmask & ((cand < 0) | (cand >= vocab))).any()):
+            raise ValueError("score_candidates: a candidate token outside the vocabulary [0, %d)" % vocab)
+        if bool((cmask & (cand == self.media_token_id)).any()):
+            raise ValueError("score_candidates: a candidate holds the media token %d: it would change the image count of the rows after it"
+                             % self.media_token_id)
+        n_layers, n_kv, head_dim, host_max = cache_geometry(lm.config)
+        if P + T > host_max:
+            raise ValueError("score_candidates: prompt %d + candidate %d tokens exceed the host's %d positions" % (P, T, host_max))
+        ids = torch.where(cmask, cand, torch.zeros_like(cand))                    # (a padded slot feeds token 0; nothing real reads it)
+        labels = torch.where(cmask, cand, torch.full_like(cand, -100))
+        lengths = lengths.cpu()
+        self._encode_vision_x(vision_x=vision_x)
+        try:
+            emb = lm.get_input_embeddings().weight
+            cache = StaticKVCache(n_layers, B, n_kv, head_dim, max(P + 1, 2), emb.device, OF.compute_dtype_for(emb))
+            media = MediaCache(B, self.media_token_id, rows_per_media=1)
+            lkw = {"_last_position_only": True} if getattr(lm, "accepts_last_position_only", False) else {}
+            out = lm(input_ids=lang_x, attention_mask=attention_mask, past_key_values=cache, use_cache=True, media_cache=media, **lkw)
+            tok = torch.zeros((B, C, T), dtype=torch.float32, device=lang_x.device)
+            tok[:, :, 0] = OF.token_logprobs(out.logits[:, -1, :], labels[:, :, 0])
+            step = max(1, max_rows // (B * max(T - 1, 1)))
+            for c0 in range(0, C, step):
+                c1 = min(c0 + step, C)
+                Tc = int(lengths[:, c0:c1].max())
+                if Tc < 2:
+                    continue
+                h = lm.forward_branches(ids[:, c0:c1, :Tc - 1].contiguous(), cache, media, attention_mask)      # [B, Cc, Tc-1, D]
+                N = B * (c1 - c0) * (Tc - 1)
+                logits = lm._unembed(h.reshape(N, 1, h.shape[-1])).view(N, -1)
+                tok[:, c0:c1, 1:Tc] = OF.token_logprobs(logits, labels[:, c0:c1, 1:Tc].reshape(N, 1)).view(B, c1 - c0, Tc - 1)
+        finally:
+            lm.clear_conditioned_layers()
+        scores = tok.sum(dim=-1)
+        return (scores, tok) if return_token_logprobs else scores
 
 
 class _nullctx:

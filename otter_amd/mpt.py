@@ -486,6 +486,28 @@ class MPTModel(MPTPreTrainedModel):
         cache.end_step()
         return BaseModelOutputWithPast(last_hidden_state=x, past_key_values=cache)
 
+    @torch.no_grad()
+    def _forward_branches(self, branch_ids, cache: StaticKVCache, attention_mask):
+        """Candidate rows over a filled StaticKVCache (OtterForConditionalGeneration.score_candidates): branch_ids int64 [B, C, T], the first
+        T input tokens of C candidate continuations of each of the cache's B prompts; attention_mask [B, P] the PROMPT's mask or None.  All
+        N = B*C*T tokens go through the decoder as one-token rows [N, 1, D] in one pass: every block runs its cached-step code, with
+        `cache.attend_branches` (through `cache.branches(C, T)`) where a step has `cache.attend` -- row (b, c, t) sees prompt b and tokens
+        0..t of its own candidate.  Returns the final-norm hidden rows [B, C, T, D].  Nothing is appended: no `end_step`, the cache stays as
+        the prompt pass left it."""
+        B, C, T = branch_ids.shape
+        x = self.wte(branch_ids.reshape(B * C * T, 1))
+        slopes = self._alibi_slopes(x.device).float().contiguous()
+        key_valid = attention_mask[:, -cache.length:].to(torch.uint8) if attention_mask is not None else None
+        view, delta = cache.branches(C, T), None
+        for i, block in enumerate(self.blocks):
+            if delta is not None and getattr(block, "gated_cross_attn_layer", None) is not None and not _gated_takes_deferred(block, x, delta):
+                x = x + delta
+                delta = None
+            out = block(x, deferred=delta, defer_out=True, static=(view, i, slopes, key_valid))
+            x, delta = out[0], out[3]
+        _, x = self.norm_f.add_forward(x, delta)
+        return x.view(B, C, T, -1)
+
     def forward(self, input_ids, past_key_values=None, attention_mask=None, use_cache=None, return_dict=True, **unused):
         use_cache = use_cache if use_cache is not None else self.config.use_cache
         if attention_mask is not None and self.training and int(attention_mask[:, 0].sum()) != attention_mask.shape[0]:
@@ -563,6 +585,12 @@ class MPTForCausalLM(MPTPreTrainedModel):
 
     def set_decoder(self, decoder):
         self.transformer = decoder
+
+    def _unembed(self, h):
+        """Hidden rows [..., D] -> logits [..., V] through this host's own head, as `forward` computes them (the tied table or its int8 copy,
+        then `logit_scale`): what `score_candidates` un-embeds its candidate rows with."""
+        logits = self.transformer.wte(h, True)
+        return logits * self.logit_scale if self.logit_scale is not None else logits
 
     def forward(self, input_ids, past_key_values=None, attention_mask=None, labels=None, use_cache=None, return_dict=True,
                 _last_position_only=False, **unused):

@@ -386,6 +386,20 @@ def flash_attn_fwd(q, k, v, slopes, key_valid, scale, causal=True):
     return o, lse
 
 
+def flash_attn_fwd_f32(q, k, v, slopes, key_valid, scale, causal=True):
+    """`flash_attn_fwd` at head_dim 128 with the output unrounded (otter_flash_attn_fwd_f32): returns (o fp32 [B,Sq,H,128] contiguous, lse
+    [B,H,Sq] fp32).  Its probabilities enter the second product as a bf16 hi + lo pair, so o is fp32-accurate.  For a consumer that goes on
+    computing with o and rounds at its own output (`branch_attn_merge`)."""
+    B, Sq, H, hd = q.shape
+    if hd != 128:
+        raise K.OtterHipError(f"flash attention with fp32 output: head_dim 128 only (got {hd})")
+    o = torch.empty((B, Sq, H, hd), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    d = _flash_desc(q, k, v, q, lse, slopes, key_valid, scale, causal)       # (d.o is not written: any valid bf16 view stands in)
+    K.check(K.lib().otter_flash_attn_fwd_f32(C.byref(d), o.data_ptr(), K.stream()), "flash_attn_fwd_f32")
+    return o, lse
+
+
 def flash_attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, slopes, key_valid, scale, causal=True):
     """Writes dq / dk / dv (caller-provided [B,S,H,head_dim] views, e.g. the three slices of one dqkv buffer)."""
     K.require_cuda(dout, dq, dk, dv)
@@ -906,7 +920,47 @@ def decode_attn_cached_shared_i8_dyn(q, k_new, v_new, k_cache, v_cache, k_scale,
     return o
 
 
-XATTN_DECODE_MAX_KEYS = 65536         # include/otter_hip.h: M = T_img * n_per_media <= 65536
+BRANCH_ATTN_MAX_T = 64                # include/otter_hip.h: OTTER_BRANCH_ATTN_MAX_T, one lane of a wave per own key
+
+
+def _branch_attn_args(q, k_new, v_new, o1, lse1, scale, T, rows_per_sentence, slopes, out):
+    """otter_branch_attn_merge, from tensors to (the library's arguments up to the stream, o) or an OtterHipError.  Like the cached-decode
+    checkers it looks at dtype, shape, strides and alignment only, so it runs on CPU tensors (tests/test_branch_attn_abi.py)."""
+    name = "branch_attn_merge"
+    N, H = _check_new_128(name, q, k_new, v_new)
+    T, rps = int(T), int(rows_per_sentence)
+    if T < 1 or T > BRANCH_ATTN_MAX_T:
+        raise K.OtterHipError(f"{name}: T={T} outside [1, {BRANCH_ATTN_MAX_T}]")
+    if N < 1 or N % T:
+        raise K.OtterHipError(f"{name}: N={N} rows are not whole candidates of T={T}")
+    if rps < T or rps % T or N % rps:
+        raise K.OtterHipError(f"{name}: rows_per_sentence={rps} must be a multiple of T={T} that divides N={N}")
+    if o1.dtype != torch.float32 or tuple(o1.shape) != (N, H, 128) or not o1.is_contiguous() or o1.data_ptr() % 16:
+        raise K.OtterHipError(f"{name}: o1 must be a contiguous fp32 [N,H,128] tensor, 16-B aligned")
+    if lse1.dtype != torch.float32 or tuple(lse1.shape) != (N // rps, H, rps) or not lse1.is_contiguous():
+        raise K.OtterHipError(f"{name}: lse1 must be a contiguous fp32 [N / rows_per_sentence, H, rows_per_sentence] tensor")
+    _check_slopes(name, slopes, H)
+    if out is None:
+        out = torch.empty((N, H, 128), dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H, 128) or not out.is_contiguous() or out.data_ptr() % 16:
+        raise K.OtterHipError(f"{name}: out must be a contiguous bf16 [N,H,128] tensor, 16-B aligned")
+    return (q.data_ptr(), q.stride(0), q.stride(1), k_new.data_ptr(), k_new.stride(0), k_new.stride(1), v_new.data_ptr(), v_new.stride(0),
+            v_new.stride(1), o1.data_ptr(), lse1.data_ptr(), K.ptr(slopes), out.data_ptr(), N, H, T, rps, 128, float(scale)), out
+
+
+def branch_attn_merge(q, k_new, v_new, o1, lse1, scale, T, rows_per_sentence, slopes=None, out=None):
+    """The own-candidate half of branch attention and its merge with the prompt half (otter_branch_attn_merge, csrc/branch_attn.hip).
+    Rows n = (b C + c) T + t.  q / k_new / v_new bf16 [N,H,128] views (unit dim stride, strides % 8 == 0, 16-B aligned: slices of the
+    projection output, read in place); o1 fp32 [N,H,128] contiguous and lse1 fp32 [B,H,C*T]: what `flash_attn_fwd_f32(q.view(B, C*T, H, 128),
+    prompt keys, prompt values, slopes, key_valid, scale, causal=False)` returns; rows_per_sentence = C * T; slopes fp32 [H] or None.
+    Returns o [N,H,128] bf16 (`out`: a contiguous bf16 [N,H,128] tensor to write instead)."""
+    K.require_cuda(q, k_new, v_new, o1, lse1, slopes, out)
+    args, o = _branch_attn_args(q, k_new, v_new, o1, lse1, scale, T, rows_per_sentence, slopes, out)
+    K.check(K.lib().otter_branch_attn_merge(*args, K.stream()), "branch_attn_merge")
+    return o
+
+
+XATTN_DECODE_MAX_KEYS = 65536        # include/otter_hip.h: M = T_img * n_per_media <= 65536
 
 
 def xattn_decode(q, k, v, H, text_time, n_per_media, rows_per_media, mask_mode, scale, out=None):
