@@ -649,21 +649,30 @@ int otter_xattn_decode(const void* q, int64_t q_stride, const void* k, const voi
  *       depend on (N, K) only: two calls give the same bits, and row m of y has the same bits whatever M is and whatever the other
  *       rows of x hold.  For M <= 16 the result equals otter_gemv_w8's to rounding, NOT bit for bit (the two sum K in different
  *       groupings).
- *   otter_gemv_w8_gated (1 <= M <= 16), otter_gemm_w8_rows_gated (1 <= M <= 64)   the same products with the gated-residual tail of the
- *       gated cross-attention block's second FFN product (the OTTER_EPI_SCALE_RES tail of otter_gemm):
+ *   otter_gemm_w8_panel   the same product, arguments, `act` codes and rules for 1 <= M <= 256: the linears of a one-token step of 65 to 256
+ *       rows.  The weight is still streamed once; a wave owns 32 output columns (128 per workgroup) and reuses every x fragment it reads
+ *       from LDS over both of its 16-row weight tiles.  workspace: at least OTTER_GEMM_W8_PANEL_WORKSPACE_BYTES(M, N, K) bytes.
+ *       Row independence: the K split (at most 8 ranges, never more workgroups than one per CU of a 256-CU part, never less than 256 K
+ *       elements per range) and every K range are functions of (N, K) alone, never of M; every output element is one accumulation chain
+ *       per range in ascending K and the ranges are added in range order.  So two calls give the same bits, and row m of y has the same
+ *       bits whatever M is, whatever the other rows of x (and R) hold -- NaN included -- and wherever the row sits in the batch.  The
+ *       split rule is this entry's own: its results equal otter_gemm_w8_rows's to rounding, NOT bit for bit.
+ *   otter_gemv_w8_gated (1 <= M <= 16), otter_gemm_w8_rows_gated (1 <= M <= 64), otter_gemm_w8_panel_gated (1 <= M <= 256)   the same
+ *       products with the gated-residual tail of the gated cross-attention block's second FFN product (the OTTER_EPI_SCALE_RES tail of otter_gemm):
  *           y[m, n] = v * s + R[m, n],   v = (x[m, :] . q[n, :]) * scale[n] (+ bias[n]),   s = gate ? tanhf(*gate) : 1,
  *       evaluated in fp32 on the fp32 sum and rounded once to y's dtype.  Arguments: those of otter_gemv_w8 without `act`, then
  *       gate (device pointer to ONE fp32, may be NULL), R (bf16 or fp32 [M, N] with row stride ldr >= N, aligned to its element, never
  *       NULL).  y and R may NOT alias: blocks that share a byte (the same tensor included) are refused.  Workspace macro, split rule,
- *       fixed-order combination of the K ranges and -- for the rows entry -- the independence of row m from M and from the other rows
- *       are those of the plain entries.  Host checks, in this order, each an OTTER_ERR_ARG with a message that names the entry:
+ *       fixed-order combination of the K ranges and -- for the rows and panel entries -- the independence of row m from M and from the
+ *       other rows are those of the plain entries.  Host checks, in this order, each an OTTER_ERR_ARG with a message that names the entry:
  *         1. x, qweight, scale, y, workspace, R not NULL          5. alignment: x, qweight, y 16-byte; ldw % 16 == 0; ldx % 8 == 0
- *         2. 1 <= M <= 16 (rows entry: 64)                        6. ldw >= K, ldx >= K, ldy >= N, ldr >= N
+ *         2. 1 <= M <= 16 (rows: 64, panel: 256)                  6. ldw >= K, ldx >= K, ldy >= N, ldr >= N
  *         3. 1 <= N <= 2^30                                       7. y / bias / R dtype is OTTER_F32 or OTTER_BF16
  *         4. K a positive multiple of 16, at most 2^30            8. y and R do not overlap       9. workspace_bytes
  *       (the plain entries run checks 1-7 without R, then `act`, then the workspace).
  *   otter_dequant_w8   out[n, k] = bf16(float(q[n, k]) * scale[n]), out bf16 [N, K] with row stride ldo (ldo % 8 == 0, 16-byte
- *       aligned): the pass in front of the library GEMM for prompt passes of more than 16 rows (and one-token steps of more than 64).
+ *       aligned): the pass in front of the library GEMM for prompt passes of more than 16 rows (and one-token steps of more than 64, or
+ *       with the panel route switched on more than 256).
  * ------------------------------------------------------------------------------------------------------- */
 #define OTTER_GEMV_W8_WORKSPACE_BYTES(M, N, K) ((int64_t)8 * (int64_t)(M) * (int64_t)(N) * 4)   /* at most 8 K ranges, whatever K */
 int otter_gemv_w8(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype, void* y,
@@ -678,6 +687,16 @@ int otter_gemv_w8_gated(const void* x, int64_t ldx, const void* qweight, int64_t
 int otter_gemm_w8_rows_gated(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias,
                              int bias_dtype, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, const float* gate,
                              const void* R, int64_t ldr, int r_dtype, void* workspace, int64_t workspace_bytes, void* stream);
+/* the panel entries split K into at most min(8, 256 / ceil(N / 128)) ranges (at least 1), whatever K and M */
+#define OTTER_GEMM_W8_PANEL_MAX_SPLIT(N) \
+    (256 / (((int64_t)(N) + 127) / 128) >= 8 ? (int64_t)8 : 256 / (((int64_t)(N) + 127) / 128) >= 1 ? 256 / (((int64_t)(N) + 127) / 128) : (int64_t)1)
+#define OTTER_GEMM_W8_PANEL_WORKSPACE_BYTES(M, N, K) (OTTER_GEMM_W8_PANEL_MAX_SPLIT(N) * (int64_t)(M) * (int64_t)(N) * 4)
+int otter_gemm_w8_panel(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype,
+                        void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int otter_gemm_w8_panel_gated(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias,
+                              int bias_dtype, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, const float* gate,
+                              const void* R, int64_t ldr, int r_dtype, void* workspace, int64_t workspace_bytes, void* stream);
 int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------

@@ -169,6 +169,9 @@ SIGNATURES = {
                                    _vp]),
     "otter_gemm_w8_rows_gated": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp,
                                         _i64, _vp]),
+    "otter_gemm_w8_panel": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
+    "otter_gemm_w8_panel_gated": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp,
+                                         _i64, _vp]),
     "otter_dequant_w8":(_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp]),
     "otter_logits_process": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp]),
     "otter_beam_step_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libotter_hip.so")
 # First in SOURCES: the longest compile starts first.
 GEMM = ["gemm_t4_s4.hip", "gemm_tiled.hip", "gemm_ph.hip", "gemm.hip"]
 SOURCES = GEMM + ["lib.hip", "norm.hip", "attn.hip", "elementwise.hip", "flash.hip", "optim.hip", "attn_mfma.hip", "loss.hip", "fuyu.hip", "decode.hip", "persimmon_decode.hip", "persimmon_decode_cache.hip", "decode_cache.hip", "decode_cache_i8.hip", "decode_cache_shared.hip", "decode_cache_shared_i8.hip", "branch_attn.hip", "xattn_decode.hip", "w8.hip", "logits.hip", "beam.hip", "select.hip", "probe.hip"]
-PIECES = {"gemm_t4_s4.hip": ["gemm_t4.hip", "gemm_s4.hip"]}   # .hip files a unit includes: they rebuild that unit only (a header or .inc rebuilds all)
+PIECES = {"gemm_t4_s4.hip": ["gemm_t4.hip", "gemm_s4.hip"], "w8.hip": ["w8_panel.hip"]}   # .hip files a unit includes: they rebuild that unit only (a header or .inc rebuilds all)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result", "-Wno-unused-value"]
 # the GEMM units: the K-major instantiations of variant 26 keep their accumulators in explicit AGPRs behind asm MFMAs; hipcc must not use the
 # AGPR half as spill space of its own there (it would, between the K loop and the tail's read-back: measured as wrong blocks)

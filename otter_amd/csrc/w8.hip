@@ -7,7 +7,8 @@
 //                 and the i8 matrix instruction is not used: q is converted to bf16 in registers (exact for |q| <= 127) and fed to
 //                 v_mfma_f32_16x16x32_bf16 with x padded to 16 rows; fp32 accumulation, the scale applied to the fp32 sum.
 // otter_gemm_w8_rows  the same product for 1 <= M <= 64: one-token steps of 17 to 64 rows (B x num_beams) still stream the weight once.
-// otter_gemv_w8_gated, otter_gemm_w8_rows_gated  the same two products with y = v tanh(*gate) + R in place of the activation: the second FFN
+// otter_gemm_w8_panel  the same product for 1 <= M <= 256: one-token steps of 65 to 256 rows (csrc/w8_panel.hip, included below).
+// otter_gemv_w8_gated, otter_gemm_w8_rows_gated, otter_gemm_w8_panel_gated  the same products with y = v tanh(*gate) + R in place of the activation: the second FFN
 //                 product of a gated cross-attention block with its tanh-gate residual.  Same kernels, GATED = true.
 // otter_dequant_w8  out[n, k] = bf16(float(q[n, k]) * scale[n]): the streaming pass behind the prompt (prefill) path.
 //
@@ -345,7 +346,7 @@ struct W8Call {
     bool gated; const float* gate; const void* R; int64_t ldr; int r_dtype;       // gated: the tail of otter_gemv_w8_gated (R must be there)
 };
 
-// the checks in the order include/otter_hip.h documents them; `what` names the entry in the message, max_m is 16 or 64
+// the checks in the order include/otter_hip.h documents them; `what` names the entry in the message, max_m is 16, 64 or 256
 int w8_check(const W8Call& c, const char* what, int max_m) {
     OTTER_REQUIRE(c.x && c.qweight && c.scale && c.y && c.workspace && (!c.gated || c.R), "%s: null pointer", what);
     OTTER_REQUIRE(c.M >= 1 && c.M <= max_m, "%s: M=%d outside [1, %d]", what, (int)c.M, max_m);
@@ -368,7 +369,8 @@ int w8_check(const W8Call& c, const char* what, int max_m) {
                       "%s: y / bias dtype must be OTTER_F32 or OTTER_BF16", what);
         OTTER_REQUIRE(c.act == 0 || c.act == 1 || c.act == 3, "%s: act=%d (0 none, 1 GELU, 3 squared ReLU)", what, c.act);
     }
-    const int64_t need = OTTER_GEMV_W8_WORKSPACE_BYTES(c.M, c.N, c.K);       // (OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES is the same expression)
+    // (OTTER_GEMM_W8_ROWS_WORKSPACE_BYTES is the GEMV's expression; the panel entries, max_m 256, have their own)
+    const int64_t need = max_m > 64 ? OTTER_GEMM_W8_PANEL_WORKSPACE_BYTES(c.M, c.N, c.K) : OTTER_GEMV_W8_WORKSPACE_BYTES(c.M, c.N, c.K);
     OTTER_REQUIRE(c.workspace_bytes >= need, "%s: workspace of %ld bytes, %ld needed", what, (long)c.workspace_bytes, (long)need);
     return OTTER_OK;
 }
@@ -454,6 +456,8 @@ int gemm_w8_rows_run(const W8Call& c, const char* what, const char* what_reduce)
     return S > 1 ? w8_reduce(a, st, what_reduce) : OTTER_OK;
 }
 
+#include "w8_panel.hip"   // gemm_w8_panel_kernel and gemm_w8_panel_run: one-token steps of 65 to 256 rows
+
 }  // namespace
 
 extern "C" {
@@ -487,6 +491,22 @@ int otter_gemm_w8_rows_gated(const void* x, int64_t ldx, const void* qweight, in
     return gemm_w8_rows_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, 0, workspace, workspace_bytes, stream,
                              true, gate, R, ldr, r_dtype},
                             "gemm_w8_rows_gated", "gemm_w8_rows_gated (reduce)");
+}
+
+int otter_gemm_w8_panel(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias, int bias_dtype,
+                        void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, int act, void* workspace, int64_t workspace_bytes,
+                        void* stream) {
+    return gemm_w8_panel_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, act, workspace, workspace_bytes, stream,
+                              false, nullptr, nullptr, 0, OTTER_F32},
+                             "gemm_w8_panel", "gemm_w8_panel (reduce)");
+}
+
+int otter_gemm_w8_panel_gated(const void* x, int64_t ldx, const void* qweight, int64_t ldw, const float* scale, const void* bias,
+                              int bias_dtype, void* y, int64_t ldy, int y_dtype, int64_t M, int64_t N, int64_t K, const float* gate,
+                              const void* R, int64_t ldr, int r_dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+    return gemm_w8_panel_run({x, ldx, qweight, ldw, scale, bias, bias_dtype, y, ldy, y_dtype, M, N, K, 0, workspace, workspace_bytes, stream,
+                              true, gate, R, ldr, r_dtype},
+                             "gemm_w8_panel_gated", "gemm_w8_panel_gated (reduce)");
 }
 
 int otter_dequant_w8(const void* qweight, int64_t ldw, const float* scale, void* out, int64_t ldo, int64_t N, int64_t K, void* stream) {

@@ -570,7 +570,7 @@ class PersimmonForCausalLM(PersimmonPreTrainedModel):
 
         return generate_tokens(step, input_ids, attention_mask, **generate_kwargs)
 
-    def quantize_decoder_int8(self, lm_head: bool = True) -> dict:
+    def quantize_decoder_int8(self, lm_head: bool = True, wide_steps: bool = False) -> dict:
         """Opt-in, for generation: hold the decoder's linears (`query_key_value`, `dense`, `dense_h_to_4h`, `dense_4h_to_h` of every layer)
         and, with `lm_head`, the untied un-embedding as int8 weights with one fp32 scale per output row (otter_amd/quant.py:
         `quantize_persimmon_decoder`), put the model in eval mode and return {"replaced", "bytes_before", "bytes_after"}.  The layers are
@@ -578,10 +578,14 @@ class PersimmonForCausalLM(PersimmonPreTrainedModel):
 
         This is an IN-MEMORY transformation done after loading: checkpoints stay in the reference's format.  `state_dict()` of a quantised
         model (qweight / scale buffers instead of weights) is not a reference-format checkpoint, so `save_pretrained` on it raises; the
-        quantised decoder is inference-only (no autograd through it).  Calling it again replaces nothing."""
-        from .quant import quantize_persimmon_decoder
+        quantised decoder is inference-only (no autograd through it).  Calling it again replaces nothing.  `wide_steps=True` sets
+        `panel_rows = quant.PANEL_MAX_ROWS` on every Int8FrozenLinear of the model, whichever call quantised it: one-token steps of 65 to
+        that many rows then run the panel kernel instead of dequantising; the returned dict does not change."""
+        from .quant import quantize_persimmon_decoder, set_wide_steps
 
         info = quantize_persimmon_decoder(self, lm_head=lm_head)
+        if wide_steps:
+            set_wide_steps(self)
         self.eval()
         return info
 
@@ -724,11 +728,11 @@ class FuyuForCausalLM(FuyuPreTrainedModel):
 
         return generate_tokens(step, input_ids, attention_mask, **generate_kwargs)
 
-    def quantize_decoder_int8(self, lm_head: bool = True) -> dict:
+    def quantize_decoder_int8(self, lm_head: bool = True, wide_steps: bool = False) -> dict:
         """`PersimmonForCausalLM.quantize_decoder_int8` on `language_model` (same contract: in-memory, eval mode, inference-only,
         `save_pretrained` raises afterwards, a second call replaces nothing); `vision_embed_tokens` and the embedding stay as they are.
         Returns {"replaced", "bytes_before", "bytes_after"}."""
-        info = self.language_model.quantize_decoder_int8(lm_head=lm_head)
+        info = self.language_model.quantize_decoder_int8(lm_head=lm_head, wide_steps=wide_steps)
         self.eval()
         return info
 

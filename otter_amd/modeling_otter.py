@@ -587,24 +587,29 @@ class OtterForConditionalGeneration(OtterPreTrainedModel):
         model.init_weights()
         return model
 
-    def quantize_decoder_int8(self, gated_blocks: bool = False, lm_head: bool = False) -> dict:
+    def quantize_decoder_int8(self, gated_blocks: bool = False, lm_head: bool = False, wide_steps: bool = False) -> dict:
         """Opt-in, for generation: hold the frozen decoder's linears as int8 weights with one fp32 scale per output row
         (otter_amd/quant.py: `quantize_frozen_decoder`), put the model in eval mode and return {"replaced", "bytes_before", "bytes_after"}:
         what THIS call replaced.  `gated_blocks=True` also replaces the two FFN linears of every gated cross-attention block
         (`quantize_gated_blocks`: trainable layers, so the keyword is the statement that training is over), `lm_head=True` the un-embedding
         (`quantize_unembedding`: an int8 copy of MPT's tied table, LLaMA's `lm_head`), of which generate() then computes only the last
         position of the prompt pass.  A later call with more keywords quantises only what is still unquantised.
+        `wide_steps=True` lets cached steps of 65 to `quant.PANEL_MAX_ROWS` rows (batch x beams) run the panel kernel instead of
+        dequantising: it sets `panel_rows` on every Int8FrozenLinear of the model, whichever call quantised it, and
+        changes nothing in the returned dict.
 
         This is an IN-MEMORY transformation done after loading: checkpoints stay in the reference's format.  `state_dict()` of a quantised
         model (qweight / scale buffers instead of weights) is not a reference-format checkpoint, so `save_pretrained` on it raises; the
         quantised decoder is inference-only (no autograd through it).  Calling it again replaces nothing."""
-        from .quant import quantize_frozen_decoder, quantize_gated_blocks, quantize_unembedding
+        from .quant import quantize_frozen_decoder, quantize_gated_blocks, quantize_unembedding, set_wide_steps
 
         parts = [quantize_frozen_decoder(self.lang_encoder)]
         if gated_blocks:
             parts.append(quantize_gated_blocks(self.lang_encoder))
         if lm_head:
             parts.append(quantize_unembedding(self.lang_encoder))
+        if wide_steps:
+            set_wide_steps(self)
         self.eval()
         return {k: sum(p[k] for p in parts) for k in ("replaced", "bytes_before", "bytes_after")}
 

@@ -1095,7 +1095,7 @@ def _w8_gated(name, max_rows, x, qweight, scale, gate, R, bias, out_dtype, out):
     if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.device != x.device:
         raise K.OtterHipError(f"{name}: out must be [M, N] with a unit column stride on x's device")
     ldx, ldy, ldr = (x.stride(0), y.stride(0), R.stride(0)) if M > 1 else (Kd, N, N)      # (the row stride of a one-row view is arbitrary)
-    ws = _ws.get(8 * M * N * 4, x.device)
+    ws = _ws.get(gemm_w8_panel_workspace_bytes(M, N, Kd) if max_rows == GEMM_W8_PANEL_MAX_ROWS else 8 * M * N * 4, x.device)
     K.check(getattr(K.lib(), "otter_" + name)(x.data_ptr(), ldx, qweight.data_ptr(), qweight.stride(0), scale.data_ptr(), K.ptr(bias),
                                               K.dt(bias) if bias is not None else K.F32, y.data_ptr(), ldy, K.dt(y), M, N, Kd, K.ptr(gate),
                                               R.data_ptr(), ldr, K.dt(R), ws.data_ptr(), ws.numel(), K.stream()), name)
@@ -1113,6 +1113,46 @@ def gemm_w8_rows_gated(x, qweight, scale, gate, R, bias=None, out_dtype=torch.bf
     """gemv_w8_gated for 1 <= M <= 64 (otter_gemm_w8_rows_gated): row m of the result has the same bits whatever M is and whatever the other
     rows of x and R hold."""
     return _w8_gated("gemm_w8_rows_gated", GEMM_W8_ROWS_MAX_ROWS, x, qweight, scale, gate, R, bias, out_dtype, out)
+
+
+GEMM_W8_PANEL_MAX_ROWS = 256          # include/otter_hip.h: 1 <= M <= 256
+
+
+def gemm_w8_panel_workspace_bytes(M: int, N: int, K: int) -> int:
+    """OTTER_GEMM_W8_PANEL_WORKSPACE_BYTES of include/otter_hip.h: at most min(8, 256 // ceil(N / 128)) K ranges (at least 1)."""
+    return min(8, max(1, 256 // ((N + 127) // 128))) * M * N * 4
+
+
+def gemm_w8_panel(x, qweight, scale, bias=None, act: int = 0, out_dtype=torch.bfloat16, out=None):
+    """gemv_w8's product, arguments, `act` codes (0, 1, 3) and rules for 1 <= M <= 256 (otter_gemm_w8_panel, csrc/w8_panel.hip): the one-token
+    steps of 65 to 256 rows.  Row m of the result has the same bits whatever M is, whatever the other rows of x hold and wherever it sits."""
+    name = "gemm_w8_panel"
+    K.require_cuda(x, qweight, scale, bias, out)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise K.OtterHipError(f"{name}: x must be bf16 [M, K] with a unit column stride")
+    if not _w8_weight_ok(qweight, scale):
+        raise K.OtterHipError(f"{name}: qweight int8 [N, K] (K % 16 == 0, row stride % 16 == 0, 16-B aligned), scale contiguous fp32 [N]")
+    M, Kd = x.shape
+    N = qweight.shape[0]
+    if Kd != qweight.shape[1] or not 1 <= M <= GEMM_W8_PANEL_MAX_ROWS:
+        raise K.OtterHipError(f"{name}: x {tuple(x.shape)} against qweight {tuple(qweight.shape)} (1 <= M <= {GEMM_W8_PANEL_MAX_ROWS})")
+    if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
+        raise K.OtterHipError(f"{name}: bias must be contiguous [N]")
+    y = torch.empty((M, N), dtype=out_dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.device != x.device:
+        raise K.OtterHipError(f"{name}: out must be [M, N] with a unit column stride on x's device")
+    ldx, ldy = (x.stride(0), y.stride(0)) if M > 1 else (Kd, N)      # (the row stride of a one-row view is arbitrary)
+    ws = _ws.get(gemm_w8_panel_workspace_bytes(M, N, Kd), x.device)
+    K.check(K.lib().otter_gemm_w8_panel(x.data_ptr(), ldx, qweight.data_ptr(), qweight.stride(0), scale.data_ptr(), K.ptr(bias),
+                                        K.dt(bias) if bias is not None else K.F32, y.data_ptr(), ldy, K.dt(y), M, N, Kd, int(act),
+                                        ws.data_ptr(), ws.numel(), K.stream()), name)
+    return y
+
+
+def gemm_w8_panel_gated(x, qweight, scale, gate, R, bias=None, out_dtype=torch.bfloat16, out=None):
+    """gemv_w8_gated for 1 <= M <= 256 (otter_gemm_w8_panel_gated), with gemm_w8_panel's independence of row m from M and from the other
+    rows of x and R."""
+    return _w8_gated("gemm_w8_panel_gated", GEMM_W8_PANEL_MAX_ROWS, x, qweight, scale, gate, R, bias, out_dtype, out)
 
 
 def dequant_w8(qweight, scale, out=None):

@@ -31,19 +31,28 @@ from . import ops
 
 GEMV_MAX_ROWS = ops.GEMV_W8_MAX_ROWS
 ROWS_MAX_ROWS = ops.GEMM_W8_ROWS_MAX_ROWS
+# what `quantize_decoder_int8(wide_steps=True)` sets `Int8FrozenLinear.panel_rows` to: the largest measured row count (of 72, 96, 128, 192,
+# 256) up to which the panel kernel is at most 1.03 x the faster of the two routes it replaces on all four MPT-7B linears; at 256 rows the
+# dequantising route is ahead on two of them (profiles/r23_w8_panel.txt).  The kernel itself takes up to 256 rows.
+PANEL_MAX_ROWS = 192
 
 
-def route(rows: int, one_token: bool) -> str:
+def route(rows: int, one_token: bool, panel_rows: int = 0) -> str:
     """Which product an Int8FrozenLinear runs for a GPU input of `rows` rows (leading dimensions flattened):
       "gemv"     rows <= 16: ops.gemv_w8;
       "rows"     17 <= rows <= 64 in a one-token step (the input has at least three dimensions and x.shape[-2] == 1, as every cached
                  step of the MPT and LLaMA hosts passes it): ops.gemm_w8_rows.  OTTER_W8_ROWS=0 sends this case to "dequant" (A/B);
-      "dequant"  everything else -- prompt passes of any size above 16 rows, steps of more than 64 rows: ops.dequant_w8 + library GEMM.
+      "panel"    64 < rows <= panel_rows in a one-token step: ops.gemm_w8_panel.  `panel_rows` is the layer's `panel_rows` attribute, 0
+                 (never) unless `quantize_decoder_int8(wide_steps=True)` set it.  OTTER_W8_PANEL=0 sends this case to "dequant" (A/B);
+      "dequant"  everything else -- prompt passes of any size above 16 rows, steps of more than max(64, panel_rows) rows: ops.dequant_w8 +
+                 library GEMM.
     """
     if rows <= GEMV_MAX_ROWS:
         return "gemv"
     if one_token and rows <= ROWS_MAX_ROWS and os.environ.get("OTTER_W8_ROWS", "1") != "0":
         return "rows"
+    if one_token and ROWS_MAX_ROWS < rows <= panel_rows and os.environ.get("OTTER_W8_PANEL", "1") != "0":
+        return "panel"
     return "dequant"
 
 
@@ -103,7 +112,12 @@ class Int8FrozenLinear(nn.Module):
         rule: the host contract (module swap, parity with the fake-quantised model, error paths) has to be testable without a GPU.  No
         product path runs the decoder on the CPU.
     forward_gated(x, gate, residual) -- the same product with the tanh-gate residual tail of a gated cross-attention block, by the same routes.
+
+    `panel_rows` (a plain attribute, 0 by default; `quantize_decoder_int8(wide_steps=True)` sets it to PANEL_MAX_ROWS): one-token steps of
+    65 to `panel_rows` rows run `ops.gemm_w8_panel` / `ops.gemm_w8_panel_gated` instead of dequantising.
     """
+
+    panel_rows = 0
 
     def __init__(self, qweight: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None):
         super().__init__()
@@ -149,11 +163,11 @@ class Int8FrozenLinear(nn.Module):
         lead = x.shape[:-1]
         x2 = x.reshape(-1, self.in_features)
         xb = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
-        how = route(xb.shape[0], x.dim() >= 3 and x.shape[-2] == 1)
+        how = route(xb.shape[0], x.dim() >= 3 and x.shape[-2] == 1, self.panel_rows)
         if how != "dequant":
             if xb.stride(1) != 1 or (xb.shape[0] > 1 and xb.stride(0) % 8) or xb.data_ptr() % 16:
                 xb = xb.contiguous()
-            product = ops.gemv_w8 if how == "gemv" else ops.gemm_w8_rows
+            product = {"gemv": ops.gemv_w8, "rows": ops.gemm_w8_rows, "panel": ops.gemm_w8_panel}[how]
             y = product(xb, self.qweight, self.scale, self.bias, _ACT_CODES[act], out_dtype=cd)
             return y.view(lead + (self.out_features,))
         n, k = self.qweight.shape
@@ -170,7 +184,8 @@ class Int8FrozenLinear(nn.Module):
     def forward_gated(self, x: torch.Tensor, gate: Optional[torch.Tensor], residual: torch.Tensor) -> torch.Tensor:
         """self(x) * tanh(gate) + residual, the tail in fp32 on the fp32 product and rounded once to residual's dtype: the second FFN
         product of a gated cross-attention block.  `gate`: one fp32 value (None: 1), `residual`: x's leading
-        dimensions x out_features.  The routes are `forward`'s: "gemv" / "rows" run `ops.gemv_w8_gated` / `ops.gemm_w8_rows_gated`,
+        dimensions x out_features.  The routes are `forward`'s: "gemv" / "rows" / "panel" run `ops.gemv_w8_gated` / `ops.gemm_w8_rows_gated` /
+        `ops.gemm_w8_panel_gated`,
         "dequant" the library GEMM of the unquantised block with its EPI_SCALE_RES tail on the dequantised weight, the CPU plain torch."""
         if torch.is_grad_enabled() and (x.requires_grad or residual.requires_grad):
             raise RuntimeError("the int8 decoder is inference-only: its input requires grad (run it under torch.no_grad(); training or LoRA "
@@ -185,13 +200,13 @@ class Int8FrozenLinear(nn.Module):
             return (v.float() * (torch.tanh(gate.float()) if gate is not None else 1.0) + residual.float()).to(rd)
         x2, r2 = x.reshape(-1, self.in_features), residual.reshape(-1, self.out_features)
         xb = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
-        how = route(xb.shape[0], x.dim() >= 3 and x.shape[-2] == 1)
+        how = route(xb.shape[0], x.dim() >= 3 and x.shape[-2] == 1, self.panel_rows)
         if r2.stride(1) != 1 or r2.dtype not in (torch.bfloat16, torch.float32):
             r2 = r2.contiguous() if r2.dtype in (torch.bfloat16, torch.float32) else r2.float()
         if how != "dequant":
             if xb.stride(1) != 1 or (xb.shape[0] > 1 and xb.stride(0) % 8) or xb.data_ptr() % 16:
                 xb = xb.contiguous()
-            product = ops.gemv_w8_gated if how == "gemv" else ops.gemm_w8_rows_gated
+            product = {"gemv": ops.gemv_w8_gated, "rows": ops.gemm_w8_rows_gated, "panel": ops.gemm_w8_panel_gated}[how]
             return product(xb, self.qweight, self.scale, gate, r2, self.bias, out_dtype=rd).view(residual.shape)
         if self.bias is not None:
             raise NotImplementedError("Int8FrozenLinear.forward_gated: a bias on the dequantising route (the gated blocks have none)")
@@ -302,7 +317,8 @@ class Int8Unembedding(Int8FrozenLinear):
     """The un-embedding (MPT: an int8 copy of the tied table, LLaMA: `lm_head`) as an Int8FrozenLinear that never dequantises: on the GPU
     at most 16 rows run `ops.gemv_w8`, more run `ops.gemm_w8_rows` in slices of at most 64 rows (the rows of that kernel do not depend on
     each other), so a pass of any size leaves the shared dequantisation scratch at the largest decoder weight.  generate() sends only the
-    last position of the prompt pass here."""
+    last position of the prompt pass here.  With `panel_rows` set (and OTTER_W8_PANEL not 0) a pass of more than 64 rows is cut into slices
+    of `panel_rows` rows through `ops.gemm_w8_panel`, whose rows do not depend on each other either."""
 
     def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
         if not x.is_cuda or act is not None or x.numel() // self.in_features <= GEMV_MAX_ROWS:
@@ -314,8 +330,10 @@ class Int8Unembedding(Int8FrozenLinear):
         if xb.stride(1) != 1 or xb.stride(0) % 8 or xb.data_ptr() % 16:
             xb = xb.contiguous()
         y = torch.empty((xb.shape[0], self.out_features), dtype=OF.compute_dtype_for(x), device=x.device)
-        for r in range(0, xb.shape[0], ROWS_MAX_ROWS):
-            ops.gemm_w8_rows(xb[r:r + ROWS_MAX_ROWS], self.qweight, self.scale, self.bias, 0, out=y[r:r + ROWS_MAX_ROWS])
+        wide = xb.shape[0] > ROWS_MAX_ROWS < self.panel_rows and os.environ.get("OTTER_W8_PANEL", "1") != "0"
+        step, product = (min(self.panel_rows, ops.GEMM_W8_PANEL_MAX_ROWS), ops.gemm_w8_panel) if wide else (ROWS_MAX_ROWS, ops.gemm_w8_rows)
+        for r in range(0, xb.shape[0], step):
+            product(xb[r:r + step], self.qweight, self.scale, self.bias, 0, out=y[r:r + step])
         return y.view(x.shape[:-1] + (self.out_features,))
 
 
@@ -361,3 +379,14 @@ def quantize_persimmon_decoder(lm: nn.Module, lm_head: bool = True) -> dict:
     if lm_head:
         swap(lm, "lm_head")
     return tally.info()
+
+
+def set_wide_steps(model: nn.Module, rows: int = PANEL_MAX_ROWS) -> int:
+    """Set `panel_rows = rows` on every Int8FrozenLinear of `model` (the decoder's, the gated blocks', the un-embedding, whichever call
+    quantised them): what the hosts' `quantize_decoder_int8(wide_steps=True)` does.  Returns how many there are."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m, Int8FrozenLinear):
+            m.panel_rows = rows
+            n += 1
+    return n
